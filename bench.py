@@ -4,8 +4,17 @@ Measures the BASELINE.json headline metric: epoch time + throughput
 (edges/s) for Reddit-shaped GraphSAGE 3-layer h=256, sampling-rate=0.1,
 use_pp, on N partitions = N GPUs (one process per GPU over RCCL/xGMI).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1 is launched by the driver via torch.distributed.run, one rank/GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result
+line. --dump-outputs DIR additionally writes what the LAST timed step
+computed (rank 0's train-row logits, its loss and the reduced parameter
+gradients) as DIR/<name>.npy. Inputs are seeded, and that step starts
+from the seeded initial weights (see rewind() below), so two runs or two
+builds with the same arguments agree array for array up to rounding.
+--full adds the checks that are not part of the headline figure (today:
+one extra untimed step as a numerics guard).
 
 A "step" is one full training epoch over the partitioned graph (forward,
 loss, backward, gradient all-reduce, Adam step) — identical work to the
@@ -56,7 +65,61 @@ def parse():
                    default=True)
     p.add_argument("--dropout", type=float, default=0.5)
     p.add_argument("--halo-dtype", choices=["fp32", "bf16"], default="fp32")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write the last timed step's outputs as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the checks beyond the headline figure")
     return p.parse_args()
+
+
+def writable_partition_dir(path: str) -> str:
+    """`path` if the partition store can be written there, else a per-user
+    directory under the system's temporary directory. The benchmark may be
+    started from a directory that is read-only; every rank resolves the
+    same name, so the store is still shared (and reused by later runs)."""
+    import tempfile
+    try:
+        os.makedirs(path, exist_ok=True)
+        with tempfile.TemporaryFile(dir=path):
+            pass
+        return path
+    except OSError:
+        uid = os.getuid() if hasattr(os, "getuid") else 0
+        alt = os.path.join(tempfile.gettempdir(),
+                           f"bnsgcn_bench_partition_u{uid}")
+        os.makedirs(alt, exist_ok=True)
+        return alt
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, loss, logits, model):
+    """Write the last timed step's results as float32 .npy files: the loss,
+    the reduced parameter gradients (whole), and the train-row logits,
+    which get what is left of the 64 MB budget — a fixed, seeded row
+    sample when they exceed it. The updated parameters are left out on
+    purpose: Adam's first update is lr * g / (|g| + eps), a sign function
+    of every gradient element that is zero up to rounding, so they cannot
+    be compared between runs; the gradients they come from can."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().float().cpu().reshape(1).numpy()}
+    for name, prm in model.named_parameters():
+        if prm.grad is not None:
+            arrays["grad." + name] = prm.grad.detach().float().cpu().numpy()
+    left = DUMP_BUDGET_BYTES - sum(v.nbytes for v in arrays.values())
+    logits = logits.detach().float()
+    row_bytes = 4 * max(logits.numel() // max(logits.shape[0], 1), 1)
+    max_rows = max(left // row_bytes, 0)
+    if logits.shape[0] > max_rows:
+        rows = np.sort(np.random.RandomState(0).choice(
+            logits.shape[0], size=max_rows, replace=False))
+        logits = logits[torch.from_numpy(rows).to(logits.device)]
+    arrays["logits"] = logits.cpu().numpy()
+    assert sum(v.nbytes for v in arrays.values()) <= DUMP_BUDGET_BYTES
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def main():
@@ -85,7 +148,7 @@ def main():
     args.n_partitions = world
     args.partition_method = a.partition_method
     args.data_scale = a.data_scale
-    args.partition_dir = a.partition_dir
+    args.partition_dir = writable_partition_dir(a.partition_dir)
     args.use_pp = a.use_pp
     args.dropout = a.dropout
     args.halo_dtype = a.halo_dtype
@@ -162,7 +225,29 @@ def main():
         state.prefetch(epoch + 1)
         reducer.synchronize()
         optimizer.step()
-        return loss
+        return loss, logits
+
+    # The kernels combine fp32 partial sums with atomics, so two runs
+    # differ by rounding in every step, and training amplifies that from
+    # step to step (Adam normalises each gradient element) until weights
+    # and logits differ in the third digit. A run that dumps therefore
+    # starts its last timed step from the seeded initial weights and a
+    # zeroed optimizer state: what that step computes depends on the
+    # seeded inputs alone and is the same, up to rounding, in every run
+    # and for every --steps/--warmup. The rewind is a few small device
+    # copies queued between two steps; a run without --dump-outputs
+    # never takes it.
+    initial = [t.detach().clone() for t in model.state_dict().values()] \
+        if a.dump_outputs else None
+
+    @torch.no_grad()
+    def rewind():
+        for cur, ini in zip(model.state_dict().values(), initial):
+            cur.copy_(ini)
+        for st in optimizer.state.values():
+            for v in st.values():
+                if torch.is_tensor(v):
+                    v.zero_()
 
     for e in range(a.warmup):
         step(e)
@@ -172,16 +257,28 @@ def main():
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
-    for e in range(a.steps):
+    for e in range(a.steps - 1):
         step(a.warmup + e)
+    # only the last timed step's results are kept, so the steps before it
+    # free theirs exactly as an undumped run does
+    if initial is not None:
+        rewind()
+    last = step(a.warmup + a.steps - 1) if a.steps > 0 else None
     if cuda:
         torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    final_loss = step(a.warmup + a.steps)   # untimed: numerics guard
-    assert torch.isfinite(final_loss), \
-        f"non-finite loss after {a.steps} steps — bench result invalid"
+    if last is not None:
+        assert torch.isfinite(last[0]), \
+            f"non-finite loss after {a.steps} steps — bench result invalid"
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, last[0], last[1], model)
+    del last
+    if a.full:
+        final_loss, _ = step(a.warmup + a.steps)   # untimed: numerics guard
+        assert torch.isfinite(final_loss), \
+            f"non-finite loss after {a.steps} steps — bench result invalid"
 
     # MAX over ranks (NCCL needs a device-resident tensor)
     t = torch.tensor([elapsed], device=device if cuda else "cpu")
