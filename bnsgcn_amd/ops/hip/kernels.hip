@@ -1300,6 +1300,10 @@ __global__ void bincount_i32_kernel(const int32_t* __restrict__ v, int64_t n,
 // + reduce chain reads/writes the [N,H,D] product twice per direction).
 // Wave per node row; per-lane partial accumulators indexed by the head a
 // float4 slot belongs to (H <= 8), wave-reduced per head.
+// ALIGNED (D % 4 == 0): a float4 slot lies inside one head. Otherwise
+// only (H*D) % 4 == 0 holds (e.g. the GAT output layer, D = n_class) and
+// a slot can straddle two heads, so the head is derived per component.
+template <bool ALIGNED>
 __global__ __launch_bounds__(256) void attn_project_fwd_kernel(
     const float* __restrict__ z, const float* __restrict__ al,
     const float* __restrict__ ar, float* __restrict__ el,
@@ -1315,12 +1319,24 @@ __global__ __launch_bounds__(256) void attn_project_fwd_kernel(
 #pragma unroll
     for (int h = 0; h < 8; ++h) { accl[h] = 0.f; accr[h] = 0.f; }
     for (int f = lane; f < hd4; f += WAVE) {
-      const int h = (f * 4) / D;
       const float4 zv = z4[r * hd4 + f];
       const float4 lv = al4[f];
       const float4 rv = ar4[f];
-      accl[h] += zv.x * lv.x + zv.y * lv.y + zv.z * lv.z + zv.w * lv.w;
-      accr[h] += zv.x * rv.x + zv.y * rv.y + zv.z * rv.z + zv.w * rv.w;
+      if (ALIGNED) {
+        const int h = (f * 4) / D;
+        accl[h] += zv.x * lv.x + zv.y * lv.y + zv.z * lv.z + zv.w * lv.w;
+        accr[h] += zv.x * rv.x + zv.y * rv.y + zv.z * rv.z + zv.w * rv.w;
+      } else {
+        const float zc[4] = {zv.x, zv.y, zv.z, zv.w};
+        const float lc[4] = {lv.x, lv.y, lv.z, lv.w};
+        const float rc[4] = {rv.x, rv.y, rv.z, rv.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int h = (f * 4 + j) / D;
+          accl[h] += zc[j] * lc[j];
+          accr[h] += zc[j] * rc[j];
+        }
+      }
     }
     for (int h = 0; h < H; ++h) {
       const float sl = wave_reduce_sum(accl[h]);
@@ -1333,7 +1349,9 @@ __global__ __launch_bounds__(256) void attn_project_fwd_kernel(
   }
 }
 
-// dz[n,h,d] = al[h,d]*g_el[n,h] + ar[h,d]*g_er[n,h] (single pass)
+// dz[n,h,d] = al[h,d]*g_el[n,h] + ar[h,d]*g_er[n,h] (single pass);
+// ALIGNED as in the forward kernel
+template <bool ALIGNED>
 __global__ __launch_bounds__(256) void attn_project_dz_kernel(
     const float* __restrict__ al, const float* __restrict__ ar,
     const float* __restrict__ g_el, const float* __restrict__ g_er,
@@ -1346,15 +1364,27 @@ __global__ __launch_bounds__(256) void attn_project_dz_kernel(
   float4* __restrict__ dz4 = reinterpret_cast<float4*>(dz);
   for (int64_t r = wave; r < n; r += n_waves) {
     for (int f = lane; f < hd4; f += WAVE) {
-      const int h = (f * 4) / D;
-      const float gl = g_el[r * H + h];
-      const float gr = g_er[r * H + h];
       const float4 lv = al4[f];
       const float4 rv = ar4[f];
-      dz4[r * hd4 + f] = make_float4(lv.x * gl + rv.x * gr,
-                                     lv.y * gl + rv.y * gr,
-                                     lv.z * gl + rv.z * gr,
-                                     lv.w * gl + rv.w * gr);
+      if (ALIGNED) {
+        const int h = (f * 4) / D;
+        const float gl = g_el[r * H + h];
+        const float gr = g_er[r * H + h];
+        dz4[r * hd4 + f] = make_float4(lv.x * gl + rv.x * gr,
+                                       lv.y * gl + rv.y * gr,
+                                       lv.z * gl + rv.z * gr,
+                                       lv.w * gl + rv.w * gr);
+      } else {
+        const float lc[4] = {lv.x, lv.y, lv.z, lv.w};
+        const float rc[4] = {rv.x, rv.y, rv.z, rv.w};
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int h = (f * 4 + j) / D;
+          o[j] = lc[j] * g_el[r * H + h] + rc[j] * g_er[r * H + h];
+        }
+        dz4[r * hd4 + f] = make_float4(o[0], o[1], o[2], o[3]);
+      }
     }
   }
 }
@@ -1783,6 +1813,7 @@ at::Tensor syncbn_stats(at::Tensor x) {
   const int64_t n = x.size(0);
   const int F = x.size(1);
   auto out = at::zeros({2, F}, x.options());
+  if (n == 0 || F == 0) return out;  // no zero-sized grid dimension
   auto stream = at::cuda::getCurrentCUDAStream();
   // enough row-chunks to fill 256 CUs even for one 256-wide column block
   const int row_chunks = (int)std::min<int64_t>((n + 255) / 256, 2048);
@@ -1834,6 +1865,7 @@ std::vector<at::Tensor> ln_bwd(at::Tensor x, at::Tensor dy, at::Tensor gamma,
   const int F = (int)x.size(1);
   auto dx = at::empty_like(x);
   auto dw = at::zeros({2, F}, x.options());
+  if (n == 0 || F == 0) return {dx, dw[0], dw[1]};  // no zero-sized grid
   auto stream = at::cuda::getCurrentCUDAStream();
   const int blocks = (int)std::min<int64_t>((n + 3) / 4, 32768);
   if (F % 4 == 0) {
@@ -2163,7 +2195,9 @@ std::vector<at::Tensor> attn_project(at::Tensor z, at::Tensor al,
   auto er = at::empty({n, H}, z.options());
   if (n == 0) return {el, er};
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(attn_project_fwd_kernel, dim3(spmm_grid((int)std::min<int64_t>(n, 1 << 28))),
+  auto kfn = (D % 4 == 0) ? attn_project_fwd_kernel<true>
+                          : attn_project_fwd_kernel<false>;
+  hipLaunchKernelGGL(kfn, dim3(spmm_grid((int)std::min<int64_t>(n, 1 << 28))),
                      dim3(256), 0, stream, z.data_ptr<float>(),
                      al.data_ptr<float>(), ar.data_ptr<float>(),
                      el.data_ptr<float>(), er.data_ptr<float>(), n, H, D,
@@ -2178,12 +2212,15 @@ std::vector<at::Tensor> attn_project_backward(at::Tensor z, at::Tensor al,
   const int64_t n = z.size(0);
   const int H = z.size(1), D = z.size(2);
   const int HD = H * D;
+  TORCH_CHECK(H <= 8 && HD % 4 == 0, "attn_project shape limits");
   auto dz = at::empty_like(z);
   auto dal = at::zeros({1, H, D}, z.options());
   auto dar = at::zeros({1, H, D}, z.options());
   if (n == 0) return {dz, dal, dar};
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(attn_project_dz_kernel,
+  auto kfn = (D % 4 == 0) ? attn_project_dz_kernel<true>
+                          : attn_project_dz_kernel<false>;
+  hipLaunchKernelGGL(kfn,
                      dim3(spmm_grid((int)std::min<int64_t>(n, 1 << 28))),
                      dim3(256), 0, stream, al.data_ptr<float>(),
                      ar.data_ptr<float>(), g_el.data_ptr<float>(),

@@ -501,7 +501,9 @@ def test_gpu_matches_cpu_training_at_scale():
 @pytest.mark.parametrize("H,D", [(4, 128), (4, 100), (2, 8), (1, 64)])
 def test_gat_kernels_match_reference(H, D):
     """GAT kernel set at the shapes the Yelp config actually hits (incl.
-    D=100, the non-pow2 output layer that takes the general path)."""
+    D=100, the non-pow2 output layer: D % 4 == 0, so it takes the vec4
+    spmm_edge / sddmm_dot forms, not the scalar general ones — those are
+    covered in test_gpu_kernel_paths.py)."""
     from bnsgcn_amd.ops.functional import (spmm_edge_raw, sddmm_dot_raw,
                                            sddmm_add_raw, segment_softmax_raw,
                                            segment_softmax_bwd_raw)
@@ -614,7 +616,9 @@ def test_train_and_eval_on_gpu_accuracy():
 
 
 @needs_gpu
-@pytest.mark.parametrize("H", [4, 3, 1, 16])   # pow2 -> interleaved kernel
+# H == 4 -> float4 kernel, every other H -> general kernel (the interleaved
+# pow2 kernel only runs under BNSGCN_SOFTMAX_ILV=1: test_gpu_kernel_paths.py)
+@pytest.mark.parametrize("H", [4, 3, 1, 16])
 def test_segment_softmax2_matches_reference(H):
     from bnsgcn_amd.ops.functional import segment_softmax2_raw
     ip1, _ = rand_csr(300, 10, 4000, seed=41)
