@@ -51,7 +51,7 @@ def _exchange(send: torch.Tensor, recv_counts, send_counts,
     recv = torch.empty(sum(recv_counts), send.shape[1],
                        dtype=wire.dtype, device=send.device)
     all_to_all_rows(recv, wire, recv_counts, send_counts)
-    return recv if wire_dtype is None else recv.float()
+    return recv if wire_dtype is None else recv.to(send.dtype)
 
 
 class _PartitionAggregate(Function):
