@@ -583,6 +583,16 @@ DEV_INLINE bool drop_keep(int64_t idx, uint32_t thr, uint64_t seed) {
   return (uint32_t)(z >> 32) < thr;
 }
 
+// `keep` reaches every kernel as a float, and dropout is active iff THAT
+// float is below 1: a double just under 1 rounds to exactly 1.0f, and
+// 1.0f * 2^32 does not fit a uint32_t (the conversion is undefined). The
+// launchers decide on the same rounded value, so the kernels and the
+// allocation of da1/da2 cannot disagree. keep <= 0 drops everything.
+DEV_INLINE uint32_t drop_threshold(float keep) {
+  return (keep > 0.f && keep < 1.0f)
+             ? (uint32_t)((double)keep * 4294967296.0) : 0u;
+}
+
 DEV_INLINE float4 f4_max(float4 a, float4 b) {
   return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z),
                      fmaxf(a.w, b.w));
@@ -627,7 +637,7 @@ __global__ void segment_softmax2_h4_kernel(
   const int lane = threadIdx.x & (WAVE - 1);
   const int n_waves = (gridDim.x * blockDim.x) / WAVE;
   const bool drop = keep < 1.0f;
-  const uint32_t thr = (uint32_t)(keep * 4294967296.0);
+  const uint32_t thr = drop_threshold(keep);
   const float inv_keep = drop ? 1.0f / keep : 1.0f;
   for (int r = wave; r < n_rows; r += n_waves) {
     const int64_t b1 = ip1[r], e1 = ip1[r + 1];
@@ -696,7 +706,7 @@ __global__ void segment_softmax2_h4_bwd_kernel(
   const int lane = threadIdx.x & (WAVE - 1);
   const int n_waves = (gridDim.x * blockDim.x) / WAVE;
   const bool drop = keep < 1.0f;
-  const uint32_t thr = (uint32_t)(keep * 4294967296.0);
+  const uint32_t thr = drop_threshold(keep);
   const float inv_keep = drop ? 1.0f / keep : 1.0f;
   for (int r = wave; r < n_rows; r += n_waves) {
     const int64_t b1 = ip1[r], e1 = ip1[r + 1];
@@ -775,7 +785,7 @@ __global__ void segment_softmax2_ilv_kernel(
   const int el = lane / H;               // this lane's edge slot
   const int h = lane & (H - 1);
   const bool drop = keep < 1.0f;
-  const uint32_t thr = (uint32_t)(keep * 4294967296.0);
+  const uint32_t thr = drop_threshold(keep);
   const float inv_keep = drop ? 1.0f / keep : 1.0f;
   for (int r = wave; r < n_rows; r += n_waves) {
     const int64_t b1 = ip1[r], e1 = ip1[r + 1];
@@ -827,7 +837,7 @@ __global__ void segment_softmax2_ilv_bwd_kernel(
   const int el = lane / H;
   const int h = lane & (H - 1);
   const bool drop = keep < 1.0f;
-  const uint32_t thr = (uint32_t)(keep * 4294967296.0);
+  const uint32_t thr = drop_threshold(keep);
   const float inv_keep = drop ? 1.0f / keep : 1.0f;
   for (int r = wave; r < n_rows; r += n_waves) {
     const int64_t b1 = ip1[r], e1 = ip1[r + 1];
@@ -879,7 +889,7 @@ __global__ void segment_softmax2_kernel(const int64_t* __restrict__ ip1,
   const int lane = threadIdx.x & (WAVE - 1);
   const int n_waves = (gridDim.x * blockDim.x) / WAVE;
   const bool drop = keep < 1.0f;
-  const uint32_t thr = (uint32_t)(keep * 4294967296.0);
+  const uint32_t thr = drop_threshold(keep);
   const float inv_keep = drop ? 1.0f / keep : 1.0f;
   for (int rh = wave; rh < n_rows * H; rh += n_waves) {
     const int r = rh / H, h = rh % H;
@@ -928,7 +938,7 @@ __global__ void segment_softmax2_bwd_kernel(const int64_t* __restrict__ ip1,
   const int lane = threadIdx.x & (WAVE - 1);
   const int n_waves = (gridDim.x * blockDim.x) / WAVE;
   const bool drop = keep < 1.0f;
-  const uint32_t thr = (uint32_t)(keep * 4294967296.0);
+  const uint32_t thr = drop_threshold(keep);
   const float inv_keep = drop ? 1.0f / keep : 1.0f;
   for (int rh = wave; rh < n_rows * H; rh += n_waves) {
     const int r = rh / H, h = rh % H;
@@ -1640,12 +1650,13 @@ __global__ void ln_bwd_w_kernel(
 __global__ __launch_bounds__(256) void dropout_apply_kernel(
     const float* __restrict__ x, float* __restrict__ out, int64_t n,
     float keep, uint64_t seed) {
-  const uint32_t thr = (uint32_t)(keep * 4294967296.0);
-  const float inv_keep = 1.0f / keep;
+  const bool drop = keep < 1.0f;   // keep == 1.0f: plain copy
+  const uint32_t thr = drop_threshold(keep);
+  const float inv_keep = drop ? 1.0f / keep : 1.0f;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride)
-    out[i] = drop_keep(i, thr, seed) ? x[i] * inv_keep : 0.f;
+    out[i] = (!drop || drop_keep(i, thr, seed)) ? x[i] * inv_keep : 0.f;
 }
 
 // float4 form (n % 4 == 0): identical per-element masks (drop_keep on
@@ -1653,17 +1664,18 @@ __global__ __launch_bounds__(256) void dropout_apply_kernel(
 __global__ __launch_bounds__(256) void dropout_apply_v4_kernel(
     const float4* __restrict__ x, float4* __restrict__ out, int64_t n4,
     float keep, uint64_t seed) {
-  const uint32_t thr = (uint32_t)(keep * 4294967296.0);
-  const float inv_keep = 1.0f / keep;
+  const bool drop = keep < 1.0f;   // keep == 1.0f: plain copy
+  const uint32_t thr = drop_threshold(keep);
+  const float inv_keep = drop ? 1.0f / keep : 1.0f;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
        i += stride) {
     const float4 v = x[i];
     float4 o;
-    o.x = drop_keep(i * 4 + 0, thr, seed) ? v.x * inv_keep : 0.f;
-    o.y = drop_keep(i * 4 + 1, thr, seed) ? v.y * inv_keep : 0.f;
-    o.z = drop_keep(i * 4 + 2, thr, seed) ? v.z * inv_keep : 0.f;
-    o.w = drop_keep(i * 4 + 3, thr, seed) ? v.w * inv_keep : 0.f;
+    o.x = (!drop || drop_keep(i * 4 + 0, thr, seed)) ? v.x * inv_keep : 0.f;
+    o.y = (!drop || drop_keep(i * 4 + 1, thr, seed)) ? v.y * inv_keep : 0.f;
+    o.z = (!drop || drop_keep(i * 4 + 2, thr, seed)) ? v.z * inv_keep : 0.f;
+    o.w = (!drop || drop_keep(i * 4 + 3, thr, seed)) ? v.w * inv_keep : 0.f;
     out[i] = o;
   }
 }
@@ -1979,7 +1991,8 @@ std::vector<at::Tensor> segment_softmax2(at::Tensor ip1, at::Tensor l1,
   check_f32(l1, "l1"); check_f32(l2, "l2");
   const int n_rows = ip1.numel() - 1;
   const int H = l1.size(1);
-  const bool drop = keep < 1.0;
+  // decided on the float the kernels receive (see drop_threshold)
+  const bool drop = (float)keep < 1.0f;
   auto a1 = at::empty_like(l1);
   auto a2 = at::empty_like(l2);
   auto da1 = drop ? at::empty_like(l1) : a1;

@@ -366,6 +366,12 @@ def _case_softmax_ilv():
     for H in (1, 2, 8, 16, 32):
         check_softmax2(H)
     check_softmax2_dropout(8)
+    # explicit seed: the interleaved kernel draws the host mask too, and
+    # its row loop wraps (66,000 rows > 65,536 waves)
+    import dense_path_checks as D
+    D.check_softmax2_dropout_seeded(8)
+    D.check_softmax2_keep_rounds_to_one(8)
+    D.check_softmax2_wrapped(66000, 8, "ilv")
 
 
 def _case_spmm_strided():
