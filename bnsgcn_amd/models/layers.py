@@ -13,6 +13,10 @@ our partition-aggregate / SDDMM / segment-softmax primitives:
                α=edge-softmax_dst(e); out=Σ α·z_src + bias (DGL GATConv
                semantics with feat_drop/attn_drop, negative_slope=0.2).
 
+One deliberate difference in ORDER (same math up to rounding): a GCN/SAGE
+layer that narrows (pad4(out) < in) projects before it aggregates — see
+_project_then_aggregate and PARITY.md §2.5 item 12.
+
 Parameter init mirrors the reference (uniform ±1/sqrt(fan_in),
 layer.py:20-24,65-77; GATConv uses xavier with gain=sqrt(2)).
 """
@@ -31,6 +35,30 @@ def _uniform_init(*tensors, fan_in):
     stdv = 1.0 / math.sqrt(fan_in)
     for t in tensors:
         nn.init.uniform_(t, -stdv, stdv)
+
+
+def _pad4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
+def _project_then_aggregate(ctx: GraphContext, x, weight, mode, rows):
+    """Aggregation is linear and its src/dst scales are per-row scalars, so
+    dst·Σ src·(x[u]·Wᵀ) == (dst·Σ src·x[u])·Wᵀ: a layer that narrows
+    projects FIRST and aggregates rows of pad4(out) floats instead of
+    in_feats (the order DGL's SAGEConv/GraphConv pick when in > out; the
+    reference layer always aggregates first — PARITY.md). The weight is
+    zero-padded to a multiple of 4 rows so the SpMM takes a float4 kernel;
+    the pad columns are sliced off again. No bias here: it must not pass
+    through the aggregation."""
+    out_feats = weight.shape[0]
+    wp = torch.nn.functional.pad(weight, (0, 0, 0, _pad4(out_feats) - out_feats))
+    z = F.linear(x, wp)
+    return ctx.aggregate(z, mode, rows=rows)[:, :out_feats]
+
+
+def _projects_first(in_feats: int, out_feats: int) -> bool:
+    # by shape only: the same in train and eval, on CPU and GPU
+    return _pad4(out_feats) < in_feats
 
 
 class LayerNorm(nn.Module):
@@ -83,8 +111,12 @@ class GCNLayer(nn.Module):
             if rows is not None:
                 x = x[rows]
             return F.linear(x, self.linear.weight, self.linear.bias)
+        w, b = self.linear.weight, self.linear.bias
+        if _projects_first(w.shape[1], w.shape[0]):
+            h = _project_then_aggregate(ctx, x, w, "gcn", rows)
+            return F.bias_add(h, b) if b is not None else h
         h = ctx.aggregate(x, "gcn", rows=rows)
-        return F.linear(h, self.linear.weight, self.linear.bias)
+        return F.linear(h, w, b)
 
 
 class SAGELayer(nn.Module):
@@ -114,8 +146,14 @@ class SAGELayer(nn.Module):
             if rows is not None:
                 x = x[rows]
             return F.linear(x, self.linear.weight, self.linear.bias)
-        ah = ctx.aggregate(x, "mean", rows=rows)
         x_dst = x[rows] if rows is not None else x
+        if not self.use_pp:
+            w2, b2 = self.linear2.weight, self.linear2.bias
+            if _projects_first(w2.shape[1], w2.shape[0]):
+                h = F.linear(x_dst, self.linear1.weight, self.linear1.bias) \
+                    + _project_then_aggregate(ctx, x, w2, "mean", rows)
+                return F.bias_add(h, b2) if b2 is not None else h
+        ah = ctx.aggregate(x, "mean", rows=rows)
         if self.use_pp:  # eval path of a pp layer (reference layer.py:98-100)
             return F.linear(torch.cat((x_dst, ah), dim=1), self.linear.weight,
                             self.linear.bias)

@@ -327,6 +327,30 @@ def linear(x, weight, bias=None):
     return _Linear.apply(x, weight, bias)
 
 
+class _BiasAdd(Function):
+    """h + b for a bias added outside a GEMM (the project-then-aggregate
+    layers). The bias gradient is the K12 column-sum kernel on GPU, as in
+    _Linear: torch's generic dim-0 reduction took 0.78 ms on the
+    [154k, 41] logits gradient against 0.11 ms
+    (profiles/BENCH_SUMMARY_projfirst.md)."""
+
+    @staticmethod
+    def forward(ctx, h, bias):
+        return h + bias
+
+    @staticmethod
+    def backward(ctx, grad):
+        gb = None
+        if ctx.needs_input_grad[1]:
+            gb = get_ext().syncbn_stats(grad.contiguous())[0] \
+                if use_hip(grad) else grad.sum(0)
+        return grad, gb
+
+
+def bias_add(h, bias):
+    return _BiasAdd.apply(h, bias)
+
+
 class _LayerNormF(Function):
     """Row LayerNorm (K7) on the fused gfx950 kernels — torch's ROCm LN
     kernels measured ~27% of the ogbn-products epoch (profiles/

@@ -131,6 +131,78 @@ __global__ __launch_bounds__(256) void spmm_sum_vec4_kernel(
   }
 }
 
+// Narrow rows (f4 <= G float4, e.g. the 41->44-wide projected output
+// layer): a row is at most G lanes wide, so the half-wave form above
+// leaves most lanes without a load. Here the wave is EDGE-parallel
+// instead: it still owns one contiguous worklist range and walks one item
+// at a time (same load balance and XCD remap), but lane group g = lane/G
+// takes edges k+g of the 64-edge chunk and lane j = lane%G loads float4 j
+// of that source row — 64/G row reads per step, x4 unroll. The groups'
+// partial sums are combined at the end of the item with __shfl_xor over
+// offsets G, 2G, ... (a fixed order, so non-atomic rows stay run-to-run
+// deterministic) and group 0 writes.
+template <bool ACC, int G>
+__global__ __launch_bounds__(256) void spmm_sum_narrow_kernel(
+    const int32_t* __restrict__ wrow, const int64_t* __restrict__ wbeg,
+    const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
+    const int32_t* __restrict__ indices, const float* __restrict__ x,
+    const float* __restrict__ src_scale, const float* __restrict__ dst_scale,
+    float* __restrict__ out, int f4) {
+  constexpr int NG = WAVE / G;  // edges per step
+  const int bb = xcd_remap_block(blockIdx.x, gridDim.x);
+  const int w = bb * (blockDim.x / WAVE) + (threadIdx.x / WAVE);
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int g = lane / G, j = lane % G;
+  const bool has = j < f4;
+  const int it_beg = wave_start[w], it_end = wave_start[w + 1];
+  const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
+  float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
+
+  for (int it = it_beg; it < it_end; ++it) {
+    int row = wrow[it];
+    const bool atomic = row < 0;
+    if (atomic) row = ~row;
+    const int64_t beg = wbeg[it], end = wend[it];
+    const float ds = dst_scale ? dst_scale[row] : 1.0f;
+    float4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t e0 = beg; e0 < end; e0 += WAVE) {
+      const int nv = (int)((end - e0 < WAVE) ? (end - e0) : WAVE);
+      int cid = 0;
+      float ssc = 1.0f;
+      if (lane < nv) {
+        cid = indices[e0 + lane];
+        if (src_scale) ssc = src_scale[cid];
+      }
+#pragma unroll 4
+      for (int k = 0; k < nv; k += NG) {
+        const int kk = k + g;  // k <= WAVE - NG, so kk < WAVE
+        const int c = __shfl(cid, kk, WAVE);
+        const float ss = src_scale ? __shfl(ssc, kk, WAVE) : 1.0f;
+        if (has && kk < nv) f4_axpy(acc, ss, x4[(int64_t)c * f4 + j]);
+      }
+    }
+#pragma unroll
+    for (int off = G; off < WAVE; off <<= 1) {
+      acc.x += __shfl_xor(acc.x, off, WAVE);
+      acc.y += __shfl_xor(acc.y, off, WAVE);
+      acc.z += __shfl_xor(acc.z, off, WAVE);
+      acc.w += __shfl_xor(acc.w, off, WAVE);
+    }
+    if (g == 0 && has) {
+      const int64_t o = (int64_t)row * f4 + j;
+      if (atomic) {
+        float* p = reinterpret_cast<float*>(&out4[o]);
+        atomicAdd(p + 0, ds * acc.x); atomicAdd(p + 1, ds * acc.y);
+        atomicAdd(p + 2, ds * acc.z); atomicAdd(p + 3, ds * acc.w);
+      } else {
+        float4 v = make_float4(ds * acc.x, ds * acc.y, ds * acc.z, ds * acc.w);
+        if (ACC) { float4 pv = out4[o]; v.x += pv.x; v.y += pv.y; v.z += pv.z; v.w += pv.w; }
+        out4[o] = v;
+      }
+    }
+  }
+}
+
 // float2 form for F % 2 == 0 (but % 4 != 0, e.g. the 602-wide Reddit
 // feature matrix: rows are 8-byte but not 16-byte aligned): 4 float2
 // accumulators cover 512 floats per edge walk — the scalar form needed
@@ -1727,7 +1799,23 @@ at::Tensor spmm_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
     const char* e = getenv("BNSGCN_SPMM_SUBW32_MAX");
     return e ? atoi(e) : 32;  // f4 <= this runs the half-wave variant
   }();
+  static const int narrow_max = [] {
+    const char* e = getenv("BNSGCN_SPMM_NARROW_MAX");
+    // f4 <= this runs the edge-parallel narrow kernel (0 disables it)
+    return std::min(e ? atoi(e) : 16, 16);
+  }();
   if (F % 4 == 0) {
+    if (F / 4 <= std::min(narrow_max, subw32_max)) {
+      auto kfn = acc ? spmm_sum_narrow_kernel<true, 16>
+                     : spmm_sum_narrow_kernel<false, 16>;
+      hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), 0, stream,
+                         wrow.data_ptr<int32_t>(), wbeg.data_ptr<int64_t>(),
+                         wend.data_ptr<int64_t>(), wave_start.data_ptr<int32_t>(),
+                         indices.data_ptr<int32_t>(), x.data_ptr<float>(),
+                         opt_ptr(src_scale), opt_ptr(dst_scale),
+                         out.data_ptr<float>(), F / 4);
+      return out;
+    }
     if (F / 4 <= subw32_max && n_waves % 8 == 0) {
       const int strided = strided_env && (n_waves % 8 == 0);
       auto kfn = acc ? spmm_sum_vec4_kernel<true, 32>
