@@ -103,7 +103,8 @@ def gen(seed):
 # ----------------------------------------------------------- assertions
 
 def assert_sum_bound(got, ref64, ref64_abs, n_terms, what):
-    """Elementwise any-order summation bound (module docstring)."""
+    """Elementwise any-order summation bound (module docstring). Returns
+    the largest err/bound ratio."""
     got = got.detach().double().cpu()
     assert got.shape == ref64.shape, (what, got.shape, ref64.shape)
     assert torch.isfinite(got).all(), f"{what}: non-finite output"
@@ -116,6 +117,7 @@ def assert_sum_bound(got, ref64, ref64_abs, n_terms, what):
     assert not bad.any(), (
         f"{what}: {int(bad.sum())} of {bad.numel()} elements over the bound; "
         f"max err {float(err.max()):.3e}, max err/bound {worst:.3g}")
+    return worst
 
 
 def assert_softmax_close(got, ref64, what):
@@ -274,6 +276,40 @@ def check_segment_sum_edges(H):
                                 N_COLS)
     assert_sum_bound(got, want, want_abs, degrees(tip.cpu())[:, None],
                      f"segment_sum_edges eperm H={H}")
+
+
+# --------------------------------------------------------- attn_project
+
+def check_attn_project(H, D, n):
+    """Forward and the three gradients of ops.functional.attn_project
+    through autograd (HIP kernels at H <= 8 and H*D % 4 == 0, the
+    ops/reference.py formulas on device tensors otherwise)."""
+    from bnsgcn_amd.ops import functional as BF
+    g = gen(800 + 10 * H + D)
+    z = torch.randn(n, H, D, generator=g)
+    al = torch.randn(1, H, D, generator=g)
+    ar = torch.randn(1, H, D, generator=g)
+    g_el = torch.randn(n, H, generator=g)
+    g_er = torch.randn(n, H, generator=g)
+    zg, alg, arg = (cu(t).requires_grad_(True) for t in (z, al, ar))
+    el, er = BF.attn_project(zg, alg, arg)
+    assert el.shape == (n, H) and er.shape == (n, H)
+    (el * cu(g_el) + er * cu(g_er)).sum().backward()
+
+    tag = f"attn_project (H,D)=({H},{D}) n={n}"
+    wel, wer = ref.attn_project(dbl(z), dbl(al), dbl(ar))
+    ael, aer = ref.attn_project(dbl(z).abs(), dbl(al).abs(), dbl(ar).abs())
+    worst = [assert_sum_bound(el, wel, ael, float(D), tag + " el"),
+             assert_sum_bound(er, wer, aer, float(D), tag + " er")]
+    wdz, wdal, wdar = ref.attn_project_backward(
+        dbl(z), dbl(al), dbl(ar), dbl(g_el), dbl(g_er))
+    adz, adal, adar = ref.attn_project_backward(
+        dbl(z).abs(), dbl(al).abs(), dbl(ar).abs(), dbl(g_el).abs(),
+        dbl(g_er).abs())
+    worst += [assert_sum_bound(zg.grad, wdz, adz, 2.0, tag + " dz"),
+              assert_sum_bound(alg.grad, wdal, adal, float(n), tag + " dal"),
+              assert_sum_bound(arg.grad, wdar, adar, float(n), tag + " dar")]
+    return max(worst)
 
 
 # -------------------------------------------------------- union softmax

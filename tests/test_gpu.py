@@ -696,3 +696,45 @@ def test_syncbn_module_gpu_matches_cpu():
     torch.testing.assert_close(gg, gc, rtol=1e-4, atol=1e-4)
     torch.testing.assert_close(wg, wc, rtol=1e-4, atol=1e-3)
     torch.testing.assert_close(rvg, rvc, rtol=1e-4, atol=1e-4)
+
+
+@needs_gpu
+def test_syncbn_module_gpu_real_cotangent():
+    """SyncBatchNorm forward and backward under the loss (y * c).sum()
+    with a random c. (y.sum(), as in the test above, makes dx identically
+    zero for batch norm, so its dx comparison compares rounding noise.)
+    The inputs sit at 3 + randn, where var = E[x^2] - mean^2 cancels.
+
+    Reference: the same module on the CPU in float64. Tolerance (oracle M
+    of tests/dense_path_checks.py): per tensor, the fp32 CPU run of the
+    module is measured against the float64 run as max error / max
+    magnitude; the GPU may use 8x that, floored at 1e-5."""
+    import dense_path_checks as D
+    from bnsgcn_amd.models.sync_bn import SyncBatchNorm
+    g = torch.Generator().manual_seed(11)
+    x = 3 + torch.randn(500, 24, generator=g)
+    c = torch.randn(500, 24, generator=g)
+
+    def run(dev, dtype):
+        bn = SyncBatchNorm(24, whole_size=500).to(dev, dtype)
+        bn.train()
+        xx = x.clone().to(dev, dtype).requires_grad_(True)
+        y = bn(xx)
+        (y * c.to(dev, dtype)).sum().backward()
+        return {"y": y.detach().cpu(), "dx": xx.grad.cpu(),
+                "dweight": bn.weight.grad.cpu(), "dbias": bn.bias.grad.cpu(),
+                "running_var": bn.running_var.cpu()}
+
+    ref64 = run("cpu", torch.float64)
+    ref32 = run("cpu", torch.float32)
+    assert float(ref64["dx"].abs().max()) > 1e-3, "dx comparison is vacuous"
+    assert float((ref64["dx"].abs() > 1e-3).double().mean()) > 0.5
+    got = run("cuda:0", torch.float32)
+    failures = []
+    for name in ref64:
+        try:
+            D.assert_measured(got[name], ref64[name], ref32[name],
+                              f"syncbn {name}")
+        except AssertionError as e:
+            failures.append(str(e))
+    assert not failures, failures

@@ -128,32 +128,7 @@ def test_fused_attn_dropout_long_segments(H):
 # --------------------------------------------------------- attn_project
 
 def _attn_project_case(H, D, n):
-    from bnsgcn_amd.ops import functional as BF
-    from bnsgcn_amd.ops import reference as ref
-    g = gen(800 + 10 * H + D)
-    z = torch.randn(n, H, D, generator=g)
-    al = torch.randn(1, H, D, generator=g)
-    ar = torch.randn(1, H, D, generator=g)
-    g_el = torch.randn(n, H, generator=g)
-    g_er = torch.randn(n, H, generator=g)
-    zg, alg, arg = (cu(t).requires_grad_(True) for t in (z, al, ar))
-    el, er = BF.attn_project(zg, alg, arg)
-    assert el.shape == (n, H) and er.shape == (n, H)
-    (el * cu(g_el) + er * cu(g_er)).sum().backward()
-
-    tag = f"attn_project (H,D)=({H},{D}) n={n}"
-    wel, wer = ref.attn_project(dbl(z), dbl(al), dbl(ar))
-    ael, aer = ref.attn_project(dbl(z).abs(), dbl(al).abs(), dbl(ar).abs())
-    K.assert_sum_bound(el, wel, ael, float(D), tag + " el")
-    K.assert_sum_bound(er, wer, aer, float(D), tag + " er")
-    wdz, wdal, wdar = ref.attn_project_backward(
-        dbl(z), dbl(al), dbl(ar), dbl(g_el), dbl(g_er))
-    adz, adal, adar = ref.attn_project_backward(
-        dbl(z).abs(), dbl(al).abs(), dbl(ar).abs(), dbl(g_el).abs(),
-        dbl(g_er).abs())
-    K.assert_sum_bound(zg.grad, wdz, adz, 2.0, tag + " dz")
-    K.assert_sum_bound(alg.grad, wdal, adal, float(n), tag + " dal")
-    K.assert_sum_bound(arg.grad, wdar, adar, float(n), tag + " dar")
+    K.check_attn_project(H, D, n)       # shared with the sparse sweep
 
 
 @needs_gpu
