@@ -7,6 +7,116 @@
 #define WAVE 64
 #define DEV_INLINE __device__ __forceinline__
 
+// ------------------------------------------------------------- work-list
+// View of the edge-balanced schedule built by
+// ops/csr_torch.build_worklist. Item `it` covers edges [beg[it], end[it])
+// of one destination row; wave (or SUBW-lane subgroup) w owns the
+// contiguous items wave_start[w] .. wave_start[w+1]. Two contracts with
+// the builder live here and nowhere else:
+//  * a row split over several items is stored bitwise NEGATED: its items
+//    combine with atomicAdd, every other row has one item and one writer;
+//  * n_waves is a multiple of 8, so a grid of 256-thread blocks (4 waves,
+//    or 8 half-wave subgroups) covers every wave exactly — the launchers
+//    check it (worklist_args in kernels.hip).
+struct WorkList {
+  const int32_t* __restrict__ row;
+  const int64_t* __restrict__ beg;
+  const int64_t* __restrict__ end;
+  const int32_t* __restrict__ wave_start;
+};
+
+struct WaveItems { int lane, beg, end; };            // lane within SUBW
+struct WorkItem { int row; bool atomic; int64_t beg, end; };
+
+// XCD-aware bijective block remap (dispatcher places block b on XCD b%8):
+// XCD x gets a CONTIGUOUS range of logical blocks, so consecutive waves on
+// one chiplet touch consecutive worklist items -> dst-row locality in the
+// XCD-private L2 (cdna_hip_programming.md T1; bijective form for nb%8!=0).
+DEV_INLINE int xcd_remap_block(int b, int nb) {
+  const int q = nb / 8, r = nb % 8;
+  const int xcd = b % 8, j = b / 8;
+  return (xcd < r) ? xcd * (q + 1) + j : r * (q + 1) + (xcd - r) * q + j;
+}
+
+// Item range of the calling wave (SUBW = 64) or half-wave subgroup (32).
+template <int SUBW>
+DEV_INLINE WaveItems wave_items(const WorkList& wl) {
+  const int bb = xcd_remap_block(blockIdx.x, gridDim.x);
+  const int w = bb * (blockDim.x / SUBW) + (threadIdx.x / SUBW);
+  return {(int)(threadIdx.x & (SUBW - 1)), wl.wave_start[w],
+          wl.wave_start[w + 1]};
+}
+
+DEV_INLINE WorkItem work_item(const WorkList& wl, int it) {
+  const int row = wl.row[it];
+  const bool atomic = row < 0;
+  return {atomic ? ~row : row, atomic, wl.beg[it], wl.end[it]};
+}
+
+// One SUBW-edge chunk [e0, min(e0 + SUBW, end)): lane l holds column id
+// (and src scale) of edge e0 + l from ONE coalesced load each; consumers
+// broadcast them with __shfl(., k, SUBW) for k < nv.
+struct Chunk { int cid; float ssc; int nv; };
+
+template <int SUBW>
+DEV_INLINE Chunk load_chunk(const int32_t* __restrict__ indices,
+                            const float* __restrict__ src_scale, int64_t e0,
+                            int64_t end, int lane) {
+  Chunk c = {0, 1.0f, (int)((end - e0 < SUBW) ? (end - e0) : SUBW)};
+  if (lane < c.nv) {
+    c.cid = indices[e0 + lane];
+    if (src_scale) c.ssc = src_scale[c.cid];
+  }
+  return c;
+}
+
+// ------------------------------------------------------------- row store
+DEV_INLINE void atomic_add(float* p, float v) { atomicAdd(p, v); }
+DEV_INLINE void atomic_add(float2* p, float2 v) {
+  float* f = reinterpret_cast<float*>(p);
+  atomicAdd(f + 0, v.x); atomicAdd(f + 1, v.y);
+}
+DEV_INLINE void atomic_add(float4* p, float4 v) {
+  float* f = reinterpret_cast<float*>(p);
+  atomicAdd(f + 0, v.x); atomicAdd(f + 1, v.y);
+  atomicAdd(f + 2, v.z); atomicAdd(f + 3, v.w);
+}
+
+// Write-out of s * v, one work item's result: split rows (atomic) combine
+// with atomicAdd, otherwise accumulate (ACC) or overwrite. The row scale
+// s is applied HERE because the accumulate form is one fused multiply-add
+// per element (*dst + s * v, rounded once) — passing in an already
+// rounded product would change the last bit of every accumulated row.
+template <bool ACC>
+DEV_INLINE void store_row(float* dst, float v, bool atomic, float s = 1.0f) {
+  if (atomic) atomic_add(dst, s * v);
+  else if (ACC) *dst = fmaf(s, v, *dst);
+  else *dst = s * v;
+}
+template <bool ACC>
+DEV_INLINE void store_row(float2* dst, float2 v, bool atomic, float s = 1.0f) {
+  if (atomic) {
+    atomic_add(dst, make_float2(s * v.x, s * v.y));
+  } else if (ACC) {
+    const float2 pv = *dst;
+    *dst = make_float2(fmaf(s, v.x, pv.x), fmaf(s, v.y, pv.y));
+  } else {
+    *dst = make_float2(s * v.x, s * v.y);
+  }
+}
+template <bool ACC>
+DEV_INLINE void store_row(float4* dst, float4 v, bool atomic, float s = 1.0f) {
+  if (atomic) {
+    atomic_add(dst, make_float4(s * v.x, s * v.y, s * v.z, s * v.w));
+  } else if (ACC) {
+    const float4 pv = *dst;
+    *dst = make_float4(fmaf(s, v.x, pv.x), fmaf(s, v.y, pv.y),
+                       fmaf(s, v.z, pv.z), fmaf(s, v.w, pv.w));
+  } else {
+    *dst = make_float4(s * v.x, s * v.y, s * v.z, s * v.w);
+  }
+}
+
 // ---------------------------------------------------------------- Philox
 // Philox4x32-10 — MUST match bnsgcn_amd/ops/philox.py bitwise (tests
 // assert equality). Key layout documented there.

@@ -32,101 +32,48 @@ DEV_INLINE void f4_axpy(float4& a, float ss, const float4 v) {
   a.x += ss * v.x; a.y += ss * v.y; a.z += ss * v.z; a.w += ss * v.w;
 }
 
-// XCD-aware bijective block remap (dispatcher places block b on XCD b%8):
-// XCD x gets a CONTIGUOUS range of logical blocks, so consecutive waves on
-// one chiplet touch consecutive worklist items -> dst-row locality in the
-// XCD-private L2 (cdna_hip_programming.md T1; bijective form for nb%8!=0).
-DEV_INLINE int xcd_remap_block(int b, int nb) {
-  const int q = nb / 8, r = nb % 8;
-  const int xcd = b % 8, j = b / 8;
-  return (xcd < r) ? xcd * (q + 1) + j : r * (q + 1) + (xcd - r) * q + j;
-}
-
 template <bool ACC, int SUBW>
 __global__ __launch_bounds__(256) void spmm_sum_vec4_kernel(
     const int32_t* __restrict__ wrow, const int64_t* __restrict__ wbeg,
     const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
     const int32_t* __restrict__ indices, const float* __restrict__ x,
     const float* __restrict__ src_scale, const float* __restrict__ dst_scale,
-    float* __restrict__ out, int f4, int strided) {
+    float* __restrict__ out, int f4) {
   // SUBW = scheduling width: 64 (full wave) for wide rows, 32 (half-wave
   // subgroups, independent items per half) when f4 <= 32 so narrow
   // feature dims (e.g. h=128 -> f4=32) keep every lane busy.
-  const int bb = xcd_remap_block(blockIdx.x, gridDim.x);
-  const int w = bb * (blockDim.x / SUBW) + (threadIdx.x / SUBW);
-  const int lane = threadIdx.x & (SUBW - 1);
-  // strided: the ~128 co-resident waves of an XCD walk CONSECUTIVE
-  // worklist items (stride = waves-per-XCD) instead of each owning a
-  // private contiguous range — one shared sliding src window in the
-  // XCD's 4 MB L2 rather than 128 disjoint ones (the r1 PMC profile
-  // showed 21.5% TCC hit = L2 thrash, profiles/pmc_spmm_micro_r01.txt).
-  int it_beg, it_end, it_step = 1;
-  if (strided) {
-    const int n_w = gridDim.x * (blockDim.x / SUBW);
-    const int wpx = n_w >> 3;
-    const int xcd = w / wpx, q = w - xcd * wpx;
-    it_beg = wave_start[xcd * wpx] + q;
-    it_end = wave_start[(xcd + 1) * wpx];
-    it_step = wpx;
-  } else {
-    it_beg = wave_start[w];
-    it_end = wave_start[w + 1];
-  }
+  // (A strided schedule — the waves of an XCD walking consecutive items
+  // to share one sliding src window in L2 — was measured and LOSES ~1-6%:
+  // drifting waves break their own temporal locality,
+  // profiles/BENCH_SUMMARY_r02.md.)
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<SUBW>(wl);
+  const int lane = wi.lane;
   const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
   float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
 
-  for (int it = it_beg; it < it_end; it += it_step) {
-    int row = wrow[it];
-    const bool atomic = row < 0;
-    if (atomic) row = ~row;
-    const int64_t beg = wbeg[it], end = wend[it];
-    const float ds = dst_scale ? dst_scale[row] : 1.0f;
+  for (int it = wi.beg; it < wi.end; ++it) {
+    const WorkItem wk = work_item(wl, it);
+    const float ds = dst_scale ? dst_scale[wk.row] : 1.0f;
     for (int f0 = 0; f0 < f4; f0 += 2 * SUBW) {
       const int fA = f0 + lane;
       const int fB = fA + SUBW;
       const bool hasA = fA < f4, hasB = fB < f4;
       float4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-      for (int64_t e0 = beg; e0 < end; e0 += SUBW) {
-        const int nv = (int)((end - e0 < SUBW) ? (end - e0) : SUBW);
-        int cid = 0;
-        float ssc = 1.0f;
-        if (lane < nv) {
-          cid = indices[e0 + lane];
-          if (src_scale) ssc = src_scale[cid];
-        }
+      for (int64_t e0 = wk.beg; e0 < wk.end; e0 += SUBW) {
+        const Chunk ch = load_chunk<SUBW>(indices, src_scale, e0, wk.end, lane);
 #pragma unroll 4
-        for (int k = 0; k < nv; ++k) {
-          const int c = __shfl(cid, k, SUBW);
-          const float ss = src_scale ? __shfl(ssc, k, SUBW) : 1.0f;
+        for (int k = 0; k < ch.nv; ++k) {
+          const int c = __shfl(ch.cid, k, SUBW);
+          const float ss = src_scale ? __shfl(ch.ssc, k, SUBW) : 1.0f;
           const int64_t base = (int64_t)c * f4;
           if (hasA) f4_axpy(acc0, ss, x4[base + fA]);
           if (hasB) f4_axpy(acc1, ss, x4[base + fB]);
         }
       }
-      const int64_t ob = (int64_t)row * f4;
-      if (atomic) {
-        if (hasA) {
-          float* p = reinterpret_cast<float*>(&out4[ob + fA]);
-          atomicAdd(p + 0, ds * acc0.x); atomicAdd(p + 1, ds * acc0.y);
-          atomicAdd(p + 2, ds * acc0.z); atomicAdd(p + 3, ds * acc0.w);
-        }
-        if (hasB) {
-          float* p = reinterpret_cast<float*>(&out4[ob + fB]);
-          atomicAdd(p + 0, ds * acc1.x); atomicAdd(p + 1, ds * acc1.y);
-          atomicAdd(p + 2, ds * acc1.z); atomicAdd(p + 3, ds * acc1.w);
-        }
-      } else {
-        if (hasA) {
-          float4 v = make_float4(ds * acc0.x, ds * acc0.y, ds * acc0.z, ds * acc0.w);
-          if (ACC) { float4 pv = out4[ob + fA]; v.x += pv.x; v.y += pv.y; v.z += pv.z; v.w += pv.w; }
-          out4[ob + fA] = v;
-        }
-        if (hasB) {
-          float4 v = make_float4(ds * acc1.x, ds * acc1.y, ds * acc1.z, ds * acc1.w);
-          if (ACC) { float4 pv = out4[ob + fB]; v.x += pv.x; v.y += pv.y; v.z += pv.z; v.w += pv.w; }
-          out4[ob + fB] = v;
-        }
-      }
+      const int64_t ob = (int64_t)wk.row * f4;
+      if (hasA) store_row<ACC>(&out4[ob + fA], acc0, wk.atomic, ds);
+      if (hasB) store_row<ACC>(&out4[ob + fB], acc1, wk.atomic, ds);
     }
   }
 }
@@ -149,36 +96,26 @@ __global__ __launch_bounds__(256) void spmm_sum_narrow_kernel(
     const float* __restrict__ src_scale, const float* __restrict__ dst_scale,
     float* __restrict__ out, int f4) {
   constexpr int NG = WAVE / G;  // edges per step
-  const int bb = xcd_remap_block(blockIdx.x, gridDim.x);
-  const int w = bb * (blockDim.x / WAVE) + (threadIdx.x / WAVE);
-  const int lane = threadIdx.x & (WAVE - 1);
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<WAVE>(wl);
+  const int lane = wi.lane;
   const int g = lane / G, j = lane % G;
   const bool has = j < f4;
-  const int it_beg = wave_start[w], it_end = wave_start[w + 1];
   const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
   float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
 
-  for (int it = it_beg; it < it_end; ++it) {
-    int row = wrow[it];
-    const bool atomic = row < 0;
-    if (atomic) row = ~row;
-    const int64_t beg = wbeg[it], end = wend[it];
-    const float ds = dst_scale ? dst_scale[row] : 1.0f;
+  for (int it = wi.beg; it < wi.end; ++it) {
+    const WorkItem wk = work_item(wl, it);
+    const float ds = dst_scale ? dst_scale[wk.row] : 1.0f;
     float4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int64_t e0 = beg; e0 < end; e0 += WAVE) {
-      const int nv = (int)((end - e0 < WAVE) ? (end - e0) : WAVE);
-      int cid = 0;
-      float ssc = 1.0f;
-      if (lane < nv) {
-        cid = indices[e0 + lane];
-        if (src_scale) ssc = src_scale[cid];
-      }
+    for (int64_t e0 = wk.beg; e0 < wk.end; e0 += WAVE) {
+      const Chunk ch = load_chunk<WAVE>(indices, src_scale, e0, wk.end, lane);
 #pragma unroll 4
-      for (int k = 0; k < nv; k += NG) {
+      for (int k = 0; k < ch.nv; k += NG) {
         const int kk = k + g;  // k <= WAVE - NG, so kk < WAVE
-        const int c = __shfl(cid, kk, WAVE);
-        const float ss = src_scale ? __shfl(ssc, kk, WAVE) : 1.0f;
-        if (has && kk < nv) f4_axpy(acc, ss, x4[(int64_t)c * f4 + j]);
+        const int c = __shfl(ch.cid, kk, WAVE);
+        const float ss = src_scale ? __shfl(ch.ssc, kk, WAVE) : 1.0f;
+        if (has && kk < ch.nv) f4_axpy(acc, ss, x4[(int64_t)c * f4 + j]);
       }
     }
 #pragma unroll
@@ -188,18 +125,8 @@ __global__ __launch_bounds__(256) void spmm_sum_narrow_kernel(
       acc.z += __shfl_xor(acc.z, off, WAVE);
       acc.w += __shfl_xor(acc.w, off, WAVE);
     }
-    if (g == 0 && has) {
-      const int64_t o = (int64_t)row * f4 + j;
-      if (atomic) {
-        float* p = reinterpret_cast<float*>(&out4[o]);
-        atomicAdd(p + 0, ds * acc.x); atomicAdd(p + 1, ds * acc.y);
-        atomicAdd(p + 2, ds * acc.z); atomicAdd(p + 3, ds * acc.w);
-      } else {
-        float4 v = make_float4(ds * acc.x, ds * acc.y, ds * acc.z, ds * acc.w);
-        if (ACC) { float4 pv = out4[o]; v.x += pv.x; v.y += pv.y; v.z += pv.z; v.w += pv.w; }
-        out4[o] = v;
-      }
-    }
+    if (g == 0 && has)
+      store_row<ACC>(&out4[(int64_t)wk.row * f4 + j], acc, wk.atomic, ds);
   }
 }
 
@@ -215,32 +142,22 @@ __global__ __launch_bounds__(256) void spmm_sum_vec2_kernel(
     const int32_t* __restrict__ indices, const float* __restrict__ x,
     const float* __restrict__ src_scale, const float* __restrict__ dst_scale,
     float* __restrict__ out, int f2) {
-  const int bb = xcd_remap_block(blockIdx.x, gridDim.x);
-  const int w = bb * (blockDim.x / WAVE) + (threadIdx.x / WAVE);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int it_beg = wave_start[w], it_end = wave_start[w + 1];
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<WAVE>(wl);
+  const int lane = wi.lane;
   const float2* __restrict__ x2 = reinterpret_cast<const float2*>(x);
   float2* __restrict__ out2 = reinterpret_cast<float2*>(out);
-  for (int it = it_beg; it < it_end; ++it) {
-    int row = wrow[it];
-    const bool atomic = row < 0;
-    if (atomic) row = ~row;
-    const int64_t beg = wbeg[it], end = wend[it];
-    const float ds = dst_scale ? dst_scale[row] : 1.0f;
+  for (int it = wi.beg; it < wi.end; ++it) {
+    const WorkItem wk = work_item(wl, it);
+    const float ds = dst_scale ? dst_scale[wk.row] : 1.0f;
     for (int f0 = 0; f0 < f2; f0 += 4 * WAVE) {
       float2 acc[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-      for (int64_t e0 = beg; e0 < end; e0 += WAVE) {
-        const int nv = (int)((end - e0 < WAVE) ? (end - e0) : WAVE);
-        int cid = 0;
-        float ssc = 1.0f;
-        if (lane < nv) {
-          cid = indices[e0 + lane];
-          if (src_scale) ssc = src_scale[cid];
-        }
+      for (int64_t e0 = wk.beg; e0 < wk.end; e0 += WAVE) {
+        const Chunk ch = load_chunk<WAVE>(indices, src_scale, e0, wk.end, lane);
 #pragma unroll 4
-        for (int k = 0; k < nv; ++k) {
-          const int c = __shfl(cid, k, WAVE);
-          const float ss = src_scale ? __shfl(ssc, k, WAVE) : 1.0f;
+        for (int k = 0; k < ch.nv; ++k) {
+          const int c = __shfl(ch.cid, k, WAVE);
+          const float ss = src_scale ? __shfl(ch.ssc, k, WAVE) : 1.0f;
           const int64_t base = (int64_t)c * f2;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
@@ -253,23 +170,12 @@ __global__ __launch_bounds__(256) void spmm_sum_vec2_kernel(
           }
         }
       }
-      const int64_t ob = (int64_t)row * f2;
+      const int64_t ob = (int64_t)wk.row * f2;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int f = f0 + j * WAVE + lane;
         if (f >= f2) break;
-        if (atomic) {
-          float* p = reinterpret_cast<float*>(&out2[ob + f]);
-          atomicAdd(p + 0, ds * acc[j].x);
-          atomicAdd(p + 1, ds * acc[j].y);
-        } else if (ACC) {
-          float2 pv = out2[ob + f];
-          pv.x += ds * acc[j].x;
-          pv.y += ds * acc[j].y;
-          out2[ob + f] = pv;
-        } else {
-          out2[ob + f] = make_float2(ds * acc[j].x, ds * acc[j].y);
-        }
+        store_row<ACC>(&out2[ob + f], acc[j], wk.atomic, ds);
       }
     }
   }
@@ -282,30 +188,20 @@ __global__ __launch_bounds__(256) void spmm_sum_scalar_kernel(
     const int32_t* __restrict__ indices, const float* __restrict__ x,
     const float* __restrict__ src_scale, const float* __restrict__ dst_scale,
     float* __restrict__ out, int F) {
-  const int bb = xcd_remap_block(blockIdx.x, gridDim.x);
-  const int w = bb * (blockDim.x / WAVE) + (threadIdx.x / WAVE);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int it_beg = wave_start[w], it_end = wave_start[w + 1];
-  for (int it = it_beg; it < it_end; ++it) {
-    int row = wrow[it];
-    const bool atomic = row < 0;
-    if (atomic) row = ~row;
-    const int64_t beg = wbeg[it], end = wend[it];
-    const float ds = dst_scale ? dst_scale[row] : 1.0f;
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<WAVE>(wl);
+  const int lane = wi.lane;
+  for (int it = wi.beg; it < wi.end; ++it) {
+    const WorkItem wk = work_item(wl, it);
+    const float ds = dst_scale ? dst_scale[wk.row] : 1.0f;
     for (int f0 = 0; f0 < F; f0 += 4 * WAVE) {
       float acc[4] = {0.f, 0.f, 0.f, 0.f};
-      for (int64_t e0 = beg; e0 < end; e0 += WAVE) {
-        const int nv = (int)((end - e0 < WAVE) ? (end - e0) : WAVE);
-        int cid = 0;
-        float ssc = 1.0f;
-        if (lane < nv) {
-          cid = indices[e0 + lane];
-          if (src_scale) ssc = src_scale[cid];
-        }
+      for (int64_t e0 = wk.beg; e0 < wk.end; e0 += WAVE) {
+        const Chunk ch = load_chunk<WAVE>(indices, src_scale, e0, wk.end, lane);
 #pragma unroll 2
-        for (int k = 0; k < nv; ++k) {
-          const int c = __shfl(cid, k, WAVE);
-          const float ss = src_scale ? __shfl(ssc, k, WAVE) : 1.0f;
+        for (int k = 0; k < ch.nv; ++k) {
+          const int c = __shfl(ch.cid, k, WAVE);
+          const float ss = src_scale ? __shfl(ch.ssc, k, WAVE) : 1.0f;
           const int64_t base = (int64_t)c * F;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
@@ -314,14 +210,12 @@ __global__ __launch_bounds__(256) void spmm_sum_scalar_kernel(
           }
         }
       }
-      const int64_t ob = (int64_t)row * F;
+      const int64_t ob = (int64_t)wk.row * F;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int f = f0 + j * WAVE + lane;
         if (f >= F) break;
-        if (atomic) atomicAdd(&out[ob + f], ds * acc[j]);
-        else if (ACC) out[ob + f] += ds * acc[j];
-        else out[ob + f] = ds * acc[j];
+        store_row<ACC>(&out[ob + f], acc[j], wk.atomic, ds);
       }
     }
   }
@@ -571,20 +465,16 @@ __global__ __launch_bounds__(256) void sddmm_add_kernel(
     const int32_t* __restrict__ indices, const float* __restrict__ el,
     const float* __restrict__ er, float* __restrict__ out, int H,
     float slope) {
-  const int bb = xcd_remap_block(blockIdx.x, gridDim.x);
-  const int wv = bb * (blockDim.x / WAVE) + (threadIdx.x / WAVE);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int it_beg = wave_start[wv], it_end = wave_start[wv + 1];
-  for (int it = it_beg; it < it_end; ++it) {
-    int row = wrow[it];
-    if (row < 0) row = ~row;
-    const int64_t beg = wbeg[it], end = wend[it];
-    for (int64_t e0 = beg; e0 < end; e0 += WAVE) {
-      const int64_t e = e0 + lane;
-      if (e >= end) break;
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<WAVE>(wl);
+  for (int it = wi.beg; it < wi.end; ++it) {
+    const WorkItem wk = work_item(wl, it);
+    for (int64_t e0 = wk.beg; e0 < wk.end; e0 += WAVE) {
+      const int64_t e = e0 + wi.lane;
+      if (e >= wk.end) break;
       const int64_t c = indices[e];
       for (int h = 0; h < H; ++h) {
-        float v = el[c * H + h] + er[(int64_t)row * H + h];
+        float v = el[c * H + h] + er[(int64_t)wk.row * H + h];
         if (slope >= 0.f && v < 0.f) v *= slope;
         out[e * H + h] = v;
       }
@@ -665,6 +555,21 @@ DEV_INLINE uint32_t drop_threshold(float keep) {
              ? (uint32_t)((double)keep * 4294967296.0) : 0u;
 }
 
+// Dropout of one value / one float4 whose first component has flat mask
+// index idx: kept elements are scaled by 1/keep, dropped ones are 0.
+DEV_INLINE float drop_apply(float v, int64_t idx, uint32_t thr, uint64_t seed,
+                            float inv_keep) {
+  return drop_keep(idx, thr, seed) ? v * inv_keep : 0.f;
+}
+
+DEV_INLINE float4 drop_apply(float4 v, int64_t idx, uint32_t thr,
+                             uint64_t seed, float inv_keep) {
+  return make_float4(drop_apply(v.x, idx + 0, thr, seed, inv_keep),
+                     drop_apply(v.y, idx + 1, thr, seed, inv_keep),
+                     drop_apply(v.z, idx + 2, thr, seed, inv_keep),
+                     drop_apply(v.w, idx + 3, thr, seed, inv_keep));
+}
+
 DEV_INLINE float4 f4_max(float4 a, float4 b) {
   return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z),
                      fmaxf(a.w, b.w));
@@ -693,12 +598,20 @@ DEV_INLINE float4 wave_reduce_max4(float4 v) {
   return v;
 }
 
+// The four union-softmax kernels below write each pass ONCE and run it
+// over both edge sets s = 0, 1 (fully unrolled): set s of row r is
+// [ip[s][r], ip[s][r+1]) and its dropout-mask indices start at moff[s]
+// (set 2 follows set 1 in the flat mask index space).
+
 // H == 4 (the GAT bench head count): one wave per row, each LANE loads
 // one edge's float4 of ALL FOUR heads — fully coalesced [E,4] access
 // with the SAME per-row pass count as the per-(row,head) form (64 edges
 // per pass; the head work rides in the lane's float4 ALU). The
 // per-(row,head) form reads at stride 16 B (1/4 cacheline utilization)
-// and measured ~20% of the Yelp GAT epoch.
+// and measured ~20% of the Yelp GAT epoch. (A one-wave-per-row form for
+// any power-of-two H, lanes interleaved over edge x head, was coalesced
+// too but measured SLOWER on Yelp GAT, 85 -> 112 ms epoch: short
+// power-law segments are latency-bound and lose the head parallelism.)
 __global__ void segment_softmax2_h4_kernel(
     const int64_t* __restrict__ ip1, const float4* __restrict__ l1,
     const int64_t* __restrict__ ip2, const float4* __restrict__ l2,
@@ -711,60 +624,44 @@ __global__ void segment_softmax2_h4_kernel(
   const bool drop = keep < 1.0f;
   const uint32_t thr = drop_threshold(keep);
   const float inv_keep = drop ? 1.0f / keep : 1.0f;
+  const int64_t* const ip[2] = {ip1, ip2};
+  const float4* const l[2] = {l1, l2};
+  float4* const a[2] = {a1, a2};
+  float4* const da[2] = {da1, da2};
+  const int64_t moff[2] = {0, off2};
   for (int r = wave; r < n_rows; r += n_waves) {
-    const int64_t b1 = ip1[r], e1 = ip1[r + 1];
-    const int64_t b2 = ip2[r], e2 = ip2[r + 1];
-    if (b1 == e1 && b2 == e2) continue;
+    const int64_t beg[2] = {ip[0][r], ip[1][r]};
+    const int64_t end[2] = {ip[0][r + 1], ip[1][r + 1]};
+    if (beg[0] == end[0] && beg[1] == end[1]) continue;
     float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    for (int64_t e = b1 + lane; e < e1; e += WAVE) m = f4_max(m, l1[e]);
-    for (int64_t e = b2 + lane; e < e2; e += WAVE) m = f4_max(m, l2[e]);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      for (int64_t e = beg[s] + lane; e < end[s]; e += WAVE)
+        m = f4_max(m, l[s][e]);
     m = wave_reduce_max4(m);
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int64_t e = b1 + lane; e < e1; e += WAVE) {
-      const float4 v = l1[e];
-      s.x += __expf(v.x - m.x); s.y += __expf(v.y - m.y);
-      s.z += __expf(v.z - m.z); s.w += __expf(v.w - m.w);
-    }
-    for (int64_t e = b2 + lane; e < e2; e += WAVE) {
-      const float4 v = l2[e];
-      s.x += __expf(v.x - m.x); s.y += __expf(v.y - m.y);
-      s.z += __expf(v.z - m.z); s.w += __expf(v.w - m.w);
-    }
-    s = wave_reduce_sum4(s);
+    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      for (int64_t e = beg[s] + lane; e < end[s]; e += WAVE) {
+        const float4 v = l[s][e];
+        sum.x += __expf(v.x - m.x); sum.y += __expf(v.y - m.y);
+        sum.z += __expf(v.z - m.z); sum.w += __expf(v.w - m.w);
+      }
+    sum = wave_reduce_sum4(sum);
     const float4 inv = make_float4(
-        1.0f / fmaxf(s.x, 1e-38f), 1.0f / fmaxf(s.y, 1e-38f),
-        1.0f / fmaxf(s.z, 1e-38f), 1.0f / fmaxf(s.w, 1e-38f));
-    for (int64_t e = b1 + lane; e < e1; e += WAVE) {
-      const float4 v = l1[e];
-      float4 a;
-      a.x = __expf(v.x - m.x) * inv.x; a.y = __expf(v.y - m.y) * inv.y;
-      a.z = __expf(v.z - m.z) * inv.z; a.w = __expf(v.w - m.w) * inv.w;
-      a1[e] = a;
-      if (drop) {
-        float4 d;
-        d.x = drop_keep(e * 4 + 0, thr, seed) ? a.x * inv_keep : 0.f;
-        d.y = drop_keep(e * 4 + 1, thr, seed) ? a.y * inv_keep : 0.f;
-        d.z = drop_keep(e * 4 + 2, thr, seed) ? a.z * inv_keep : 0.f;
-        d.w = drop_keep(e * 4 + 3, thr, seed) ? a.w * inv_keep : 0.f;
-        da1[e] = d;
+        1.0f / fmaxf(sum.x, 1e-38f), 1.0f / fmaxf(sum.y, 1e-38f),
+        1.0f / fmaxf(sum.z, 1e-38f), 1.0f / fmaxf(sum.w, 1e-38f));
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      for (int64_t e = beg[s] + lane; e < end[s]; e += WAVE) {
+        const float4 v = l[s][e];
+        float4 av;
+        av.x = __expf(v.x - m.x) * inv.x; av.y = __expf(v.y - m.y) * inv.y;
+        av.z = __expf(v.z - m.z) * inv.z; av.w = __expf(v.w - m.w) * inv.w;
+        a[s][e] = av;
+        if (drop)
+          da[s][e] = drop_apply(av, moff[s] + e * 4, thr, seed, inv_keep);
       }
-    }
-    for (int64_t e = b2 + lane; e < e2; e += WAVE) {
-      const float4 v = l2[e];
-      float4 a;
-      a.x = __expf(v.x - m.x) * inv.x; a.y = __expf(v.y - m.y) * inv.y;
-      a.z = __expf(v.z - m.z) * inv.z; a.w = __expf(v.w - m.w) * inv.w;
-      a2[e] = a;
-      if (drop) {
-        const int64_t i = off2 + e * 4;
-        float4 d;
-        d.x = drop_keep(i + 0, thr, seed) ? a.x * inv_keep : 0.f;
-        d.y = drop_keep(i + 1, thr, seed) ? a.y * inv_keep : 0.f;
-        d.z = drop_keep(i + 2, thr, seed) ? a.z * inv_keep : 0.f;
-        d.w = drop_keep(i + 3, thr, seed) ? a.w * inv_keep : 0.f;
-        da2[e] = d;
-      }
-    }
   }
 }
 
@@ -780,169 +677,38 @@ __global__ void segment_softmax2_h4_bwd_kernel(
   const bool drop = keep < 1.0f;
   const uint32_t thr = drop_threshold(keep);
   const float inv_keep = drop ? 1.0f / keep : 1.0f;
+  const int64_t* const ip[2] = {ip1, ip2};
+  const float4* const a[2] = {a1, a2};
+  const float4* const g[2] = {g1, g2};
+  float4* const d[2] = {d1, d2};
+  const int64_t moff[2] = {0, off2};
   for (int r = wave; r < n_rows; r += n_waves) {
-    const int64_t b1 = ip1[r], e1 = ip1[r + 1];
-    const int64_t b2 = ip2[r], e2 = ip2[r + 1];
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int64_t e = b1 + lane; e < e1; e += WAVE) {
-      const float4 av = a1[e];
-      float4 gv = g1[e];
-      if (drop) {
-        gv.x = drop_keep(e * 4 + 0, thr, seed) ? gv.x * inv_keep : 0.f;
-        gv.y = drop_keep(e * 4 + 1, thr, seed) ? gv.y * inv_keep : 0.f;
-        gv.z = drop_keep(e * 4 + 2, thr, seed) ? gv.z * inv_keep : 0.f;
-        gv.w = drop_keep(e * 4 + 3, thr, seed) ? gv.w * inv_keep : 0.f;
+    const int64_t beg[2] = {ip[0][r], ip[1][r]};
+    const int64_t end[2] = {ip[0][r + 1], ip[1][r + 1]};
+    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      for (int64_t e = beg[s] + lane; e < end[s]; e += WAVE) {
+        const float4 av = a[s][e];
+        float4 gv = g[s][e];
+        if (drop) gv = drop_apply(gv, moff[s] + e * 4, thr, seed, inv_keep);
+        sum.x += av.x * gv.x; sum.y += av.y * gv.y;
+        sum.z += av.z * gv.z; sum.w += av.w * gv.w;
       }
-      s.x += av.x * gv.x; s.y += av.y * gv.y;
-      s.z += av.z * gv.z; s.w += av.w * gv.w;
-    }
-    for (int64_t e = b2 + lane; e < e2; e += WAVE) {
-      const float4 av = a2[e];
-      float4 gv = g2[e];
-      if (drop) {
-        const int64_t i = off2 + e * 4;
-        gv.x = drop_keep(i + 0, thr, seed) ? gv.x * inv_keep : 0.f;
-        gv.y = drop_keep(i + 1, thr, seed) ? gv.y * inv_keep : 0.f;
-        gv.z = drop_keep(i + 2, thr, seed) ? gv.z * inv_keep : 0.f;
-        gv.w = drop_keep(i + 3, thr, seed) ? gv.w * inv_keep : 0.f;
+    sum = wave_reduce_sum4(sum);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      for (int64_t e = beg[s] + lane; e < end[s]; e += WAVE) {
+        const float4 av = a[s][e];
+        float4 gv = g[s][e];
+        if (drop) gv = drop_apply(gv, moff[s] + e * 4, thr, seed, inv_keep);
+        d[s][e] = make_float4(av.x * (gv.x - sum.x), av.y * (gv.y - sum.y),
+                              av.z * (gv.z - sum.z), av.w * (gv.w - sum.w));
       }
-      s.x += av.x * gv.x; s.y += av.y * gv.y;
-      s.z += av.z * gv.z; s.w += av.w * gv.w;
-    }
-    s = wave_reduce_sum4(s);
-    for (int64_t e = b1 + lane; e < e1; e += WAVE) {
-      const float4 av = a1[e];
-      float4 gv = g1[e];
-      if (drop) {
-        gv.x = drop_keep(e * 4 + 0, thr, seed) ? gv.x * inv_keep : 0.f;
-        gv.y = drop_keep(e * 4 + 1, thr, seed) ? gv.y * inv_keep : 0.f;
-        gv.z = drop_keep(e * 4 + 2, thr, seed) ? gv.z * inv_keep : 0.f;
-        gv.w = drop_keep(e * 4 + 3, thr, seed) ? gv.w * inv_keep : 0.f;
-      }
-      d1[e] = make_float4(av.x * (gv.x - s.x), av.y * (gv.y - s.y),
-                          av.z * (gv.z - s.z), av.w * (gv.w - s.w));
-    }
-    for (int64_t e = b2 + lane; e < e2; e += WAVE) {
-      const float4 av = a2[e];
-      float4 gv = g2[e];
-      if (drop) {
-        const int64_t i = off2 + e * 4;
-        gv.x = drop_keep(i + 0, thr, seed) ? gv.x * inv_keep : 0.f;
-        gv.y = drop_keep(i + 1, thr, seed) ? gv.y * inv_keep : 0.f;
-        gv.z = drop_keep(i + 2, thr, seed) ? gv.z * inv_keep : 0.f;
-        gv.w = drop_keep(i + 3, thr, seed) ? gv.w * inv_keep : 0.f;
-      }
-      d2[e] = make_float4(av.x * (gv.x - s.x), av.y * (gv.y - s.y),
-                          av.z * (gv.z - s.z), av.w * (gv.w - s.w));
-    }
   }
 }
 
-// Interleaved variant for H a power of two (<= 32): ONE wave per row
-// covers ALL heads — lane l handles (edge = l >> log2H, head = l & (H-1)),
-// so loads of the [E, H] logits are fully COALESCED (the per-(row,head)
-// form reads at stride 4*H bytes: 1/4 cacheline utilization at H=4,
-// measured 5.8 ms of the Yelp GAT epoch). Per-head reductions use
-// shfl_xor with offsets >= H, which keep the head lane-invariant.
-__global__ void segment_softmax2_ilv_kernel(
-    const int64_t* __restrict__ ip1, const float* __restrict__ l1,
-    const int64_t* __restrict__ ip2, const float* __restrict__ l2,
-    float* __restrict__ a1, float* __restrict__ a2,
-    float* __restrict__ da1, float* __restrict__ da2,
-    int n_rows, int H, float keep, uint64_t seed, int64_t off2) {
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int n_waves = (gridDim.x * blockDim.x) / WAVE;
-  const int epw = WAVE / H;              // edges per wave pass
-  const int el = lane / H;               // this lane's edge slot
-  const int h = lane & (H - 1);
-  const bool drop = keep < 1.0f;
-  const uint32_t thr = drop_threshold(keep);
-  const float inv_keep = drop ? 1.0f / keep : 1.0f;
-  for (int r = wave; r < n_rows; r += n_waves) {
-    const int64_t b1 = ip1[r], e1 = ip1[r + 1];
-    const int64_t b2 = ip2[r], e2 = ip2[r + 1];
-    if (b1 == e1 && b2 == e2) continue;
-    float m = -INFINITY;
-    for (int64_t e = b1 + el; e < e1; e += epw)
-      m = fmaxf(m, l1[e * H + h]);
-    for (int64_t e = b2 + el; e < e2; e += epw)
-      m = fmaxf(m, l2[e * H + h]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-      if (off >= H) m = fmaxf(m, __shfl_xor(m, off, WAVE));
-    float sum = 0.f;
-    for (int64_t e = b1 + el; e < e1; e += epw)
-      sum += __expf(l1[e * H + h] - m);
-    for (int64_t e = b2 + el; e < e2; e += epw)
-      sum += __expf(l2[e * H + h] - m);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-      if (off >= H) sum += __shfl_xor(sum, off, WAVE);
-    const float inv = 1.0f / fmaxf(sum, 1e-38f);
-    for (int64_t e = b1 + el; e < e1; e += epw) {
-      const float a = __expf(l1[e * H + h] - m) * inv;
-      a1[e * H + h] = a;
-      if (drop)
-        da1[e * H + h] = drop_keep(e * H + h, thr, seed) ? a * inv_keep : 0.f;
-    }
-    for (int64_t e = b2 + el; e < e2; e += epw) {
-      const float a = __expf(l2[e * H + h] - m) * inv;
-      a2[e * H + h] = a;
-      if (drop)
-        da2[e * H + h] = drop_keep(off2 + e * H + h, thr, seed)
-                             ? a * inv_keep : 0.f;
-    }
-  }
-}
-
-__global__ void segment_softmax2_ilv_bwd_kernel(
-    const int64_t* __restrict__ ip1, const float* __restrict__ a1,
-    const float* __restrict__ g1, const int64_t* __restrict__ ip2,
-    const float* __restrict__ a2, const float* __restrict__ g2,
-    float* __restrict__ d1, float* __restrict__ d2,
-    int n_rows, int H, float keep, uint64_t seed, int64_t off2) {
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int n_waves = (gridDim.x * blockDim.x) / WAVE;
-  const int epw = WAVE / H;
-  const int el = lane / H;
-  const int h = lane & (H - 1);
-  const bool drop = keep < 1.0f;
-  const uint32_t thr = drop_threshold(keep);
-  const float inv_keep = drop ? 1.0f / keep : 1.0f;
-  for (int r = wave; r < n_rows; r += n_waves) {
-    const int64_t b1 = ip1[r], e1 = ip1[r + 1];
-    const int64_t b2 = ip2[r], e2 = ip2[r + 1];
-    float sum = 0.f;
-    for (int64_t e = b1 + el; e < e1; e += epw) {
-      float g = g1[e * H + h];
-      if (drop) g = drop_keep(e * H + h, thr, seed) ? g * inv_keep : 0.f;
-      sum += a1[e * H + h] * g;
-    }
-    for (int64_t e = b2 + el; e < e2; e += epw) {
-      float g = g2[e * H + h];
-      if (drop)
-        g = drop_keep(off2 + e * H + h, thr, seed) ? g * inv_keep : 0.f;
-      sum += a2[e * H + h] * g;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-      if (off >= H) sum += __shfl_xor(sum, off, WAVE);
-    for (int64_t e = b1 + el; e < e1; e += epw) {
-      float g = g1[e * H + h];
-      if (drop) g = drop_keep(e * H + h, thr, seed) ? g * inv_keep : 0.f;
-      d1[e * H + h] = a1[e * H + h] * (g - sum);
-    }
-    for (int64_t e = b2 + el; e < e2; e += epw) {
-      float g = g2[e * H + h];
-      if (drop)
-        g = drop_keep(off2 + e * H + h, thr, seed) ? g * inv_keep : 0.f;
-      d2[e * H + h] = a2[e * H + h] * (g - sum);
-    }
-  }
-}
-
+// General H: one wave per (row, head).
 // keep < 1: additionally writes the attn-dropout-applied weights into
 // da1/da2 (the spmm input), while a1/a2 keep the pre-drop softmax (the
 // backward state) — replaces the separate torch dropout pass
@@ -963,33 +729,38 @@ __global__ void segment_softmax2_kernel(const int64_t* __restrict__ ip1,
   const bool drop = keep < 1.0f;
   const uint32_t thr = drop_threshold(keep);
   const float inv_keep = drop ? 1.0f / keep : 1.0f;
+  const int64_t* const ip[2] = {ip1, ip2};
+  const float* const l[2] = {l1, l2};
+  float* const a[2] = {a1, a2};
+  float* const da[2] = {da1, da2};
+  const int64_t moff[2] = {0, off2};
   for (int rh = wave; rh < n_rows * H; rh += n_waves) {
     const int r = rh / H, h = rh % H;
-    const int64_t b1 = ip1[r], e1 = ip1[r + 1];
-    const int64_t b2 = ip2[r], e2 = ip2[r + 1];
-    if (b1 == e1 && b2 == e2) continue;
+    const int64_t beg[2] = {ip[0][r], ip[1][r]};
+    const int64_t end[2] = {ip[0][r + 1], ip[1][r + 1]};
+    if (beg[0] == end[0] && beg[1] == end[1]) continue;
     float m = -INFINITY;
-    for (int64_t e = b1 + lane; e < e1; e += WAVE) m = fmaxf(m, l1[e * H + h]);
-    for (int64_t e = b2 + lane; e < e2; e += WAVE) m = fmaxf(m, l2[e * H + h]);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      for (int64_t e = beg[s] + lane; e < end[s]; e += WAVE)
+        m = fmaxf(m, l[s][e * H + h]);
     m = wave_reduce_max(m);
     float sum = 0.f;
-    for (int64_t e = b1 + lane; e < e1; e += WAVE) sum += __expf(l1[e * H + h] - m);
-    for (int64_t e = b2 + lane; e < e2; e += WAVE) sum += __expf(l2[e * H + h] - m);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      for (int64_t e = beg[s] + lane; e < end[s]; e += WAVE)
+        sum += __expf(l[s][e * H + h] - m);
     sum = wave_reduce_sum(sum);
     const float inv = 1.0f / fmaxf(sum, 1e-38f);
-    for (int64_t e = b1 + lane; e < e1; e += WAVE) {
-      const float a = __expf(l1[e * H + h] - m) * inv;
-      a1[e * H + h] = a;
-      if (drop)
-        da1[e * H + h] = drop_keep(e * H + h, thr, seed) ? a * inv_keep : 0.f;
-    }
-    for (int64_t e = b2 + lane; e < e2; e += WAVE) {
-      const float a = __expf(l2[e * H + h] - m) * inv;
-      a2[e * H + h] = a;
-      if (drop)
-        da2[e * H + h] = drop_keep(off2 + e * H + h, thr, seed)
-                             ? a * inv_keep : 0.f;
-    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      for (int64_t e = beg[s] + lane; e < end[s]; e += WAVE) {
+        const float av = __expf(l[s][e * H + h] - m) * inv;
+        a[s][e * H + h] = av;
+        if (drop)
+          da[s][e * H + h] =
+              drop_apply(av, moff[s] + e * H + h, thr, seed, inv_keep);
+      }
   }
 }
 
@@ -1012,34 +783,31 @@ __global__ void segment_softmax2_bwd_kernel(const int64_t* __restrict__ ip1,
   const bool drop = keep < 1.0f;
   const uint32_t thr = drop_threshold(keep);
   const float inv_keep = drop ? 1.0f / keep : 1.0f;
+  const int64_t* const ip[2] = {ip1, ip2};
+  const float* const a[2] = {a1, a2};
+  const float* const g[2] = {g1, g2};
+  float* const d[2] = {d1, d2};
+  const int64_t moff[2] = {0, off2};
   for (int rh = wave; rh < n_rows * H; rh += n_waves) {
     const int r = rh / H, h = rh % H;
-    const int64_t b1 = ip1[r], e1 = ip1[r + 1];
-    const int64_t b2 = ip2[r], e2 = ip2[r + 1];
+    const int64_t beg[2] = {ip[0][r], ip[1][r]};
+    const int64_t end[2] = {ip[0][r + 1], ip[1][r + 1]};
     float sum = 0.f;
-    for (int64_t e = b1 + lane; e < e1; e += WAVE) {
-      float g = g1[e * H + h];
-      if (drop) g = drop_keep(e * H + h, thr, seed) ? g * inv_keep : 0.f;
-      sum += a1[e * H + h] * g;
-    }
-    for (int64_t e = b2 + lane; e < e2; e += WAVE) {
-      float g = g2[e * H + h];
-      if (drop)
-        g = drop_keep(off2 + e * H + h, thr, seed) ? g * inv_keep : 0.f;
-      sum += a2[e * H + h] * g;
-    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      for (int64_t e = beg[s] + lane; e < end[s]; e += WAVE) {
+        float gv = g[s][e * H + h];
+        if (drop) gv = drop_apply(gv, moff[s] + e * H + h, thr, seed, inv_keep);
+        sum += a[s][e * H + h] * gv;
+      }
     sum = wave_reduce_sum(sum);
-    for (int64_t e = b1 + lane; e < e1; e += WAVE) {
-      float g = g1[e * H + h];
-      if (drop) g = drop_keep(e * H + h, thr, seed) ? g * inv_keep : 0.f;
-      d1[e * H + h] = a1[e * H + h] * (g - sum);
-    }
-    for (int64_t e = b2 + lane; e < e2; e += WAVE) {
-      float g = g2[e * H + h];
-      if (drop)
-        g = drop_keep(off2 + e * H + h, thr, seed) ? g * inv_keep : 0.f;
-      d2[e * H + h] = a2[e * H + h] * (g - sum);
-    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      for (int64_t e = beg[s] + lane; e < end[s]; e += WAVE) {
+        float gv = g[s][e * H + h];
+        if (drop) gv = drop_apply(gv, moff[s] + e * H + h, thr, seed, inv_keep);
+        d[s][e * H + h] = a[s][e * H + h] * (gv - sum);
+      }
   }
 }
 
@@ -1080,29 +848,24 @@ __global__ __launch_bounds__(256) void sddmm_dot_gen_kernel(
     const int32_t* __restrict__ indices, const float* __restrict__ g,
     const float* __restrict__ x, float* __restrict__ out, int H, int D,
     int HD) {
-  const int bb = xcd_remap_block(blockIdx.x, gridDim.x);
-  const int wv = bb * (blockDim.x / WAVE) + (threadIdx.x / WAVE);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int it_beg = wave_start[wv], it_end = wave_start[wv + 1];
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<WAVE>(wl);
+  const int lane = wi.lane;
   const int sg = lane >> 4;            // 4 subgroups of 16 lanes:
   const int gl = lane & 15;            // 4 (edge) pairs in flight per wave
-  for (int it = it_beg; it < it_end; ++it) {
-    int row = wrow[it];
-    if (row < 0) row = ~row;
-    const int64_t beg = wbeg[it], end = wend[it];
-    for (int64_t e0 = beg; e0 < end; e0 += WAVE) {
-      const int nv = (int)((end - e0 < WAVE) ? (end - e0) : WAVE);
-      int cid = 0;
-      if (lane < nv) cid = indices[e0 + lane];
-      for (int k0 = 0; k0 < nv; k0 += 4) {
+  for (int it = wi.beg; it < wi.end; ++it) {
+    const WorkItem wk = work_item(wl, it);
+    for (int64_t e0 = wk.beg; e0 < wk.end; e0 += WAVE) {
+      const Chunk ch = load_chunk<WAVE>(indices, nullptr, e0, wk.end, lane);
+      for (int k0 = 0; k0 < ch.nv; k0 += 4) {
         const int k = k0 + sg;
-        const bool act = k < nv;
-        const int c = __shfl(cid, act ? k : 0, WAVE);
+        const bool act = k < ch.nv;
+        const int c = __shfl(ch.cid, act ? k : 0, WAVE);
         for (int h = 0; h < H; ++h) {
           float p = 0.f;
           if (act)
             for (int d = gl; d < D; d += 16)
-              p += g[(int64_t)row * HD + h * D + d] *
+              p += g[(int64_t)wk.row * HD + h * D + d] *
                    x[(int64_t)c * HD + h * D + d];
 #pragma unroll
           for (int off = 8; off > 0; off >>= 1) p += __shfl_xor(p, off, WAVE);
@@ -1126,17 +889,13 @@ __global__ __launch_bounds__(256) void spmm_edge_vec4_kernel(
     const int32_t* __restrict__ indices, const float* __restrict__ w,
     const int64_t* __restrict__ wperm, const float* __restrict__ x,
     float* __restrict__ out, int H, int D4, int HD4) {
-  const int bb = xcd_remap_block(blockIdx.x, gridDim.x);
-  const int wv = bb * (blockDim.x / WAVE) + (threadIdx.x / WAVE);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int it_beg = wave_start[wv], it_end = wave_start[wv + 1];
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<WAVE>(wl);
+  const int lane = wi.lane;
   const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
   float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
-  for (int it = it_beg; it < it_end; ++it) {
-    int row = wrow[it];
-    const bool atomic = row < 0;
-    if (atomic) row = ~row;
-    const int64_t beg = wbeg[it], end = wend[it];
+  for (int it = wi.beg; it < wi.end; ++it) {
+    const WorkItem wk = work_item(wl, it);
     // two float4 accumulators per lane (like spmm_sum_vec4): HD4 <= 128
     // — the common [H=4, D=128] GAT shape — walks the edge list ONCE
     // instead of once per 64-float4 feature pass
@@ -1147,46 +906,20 @@ __global__ __launch_bounds__(256) void spmm_edge_vec4_kernel(
       const int hA = hasA ? fA / D4 : 0;
       const int hB = hasB ? fB / D4 : 0;
       float4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-      for (int64_t e0 = beg; e0 < end; e0 += WAVE) {
-        const int nv = (int)((end - e0 < WAVE) ? (end - e0) : WAVE);
-        int cid = 0;
-        if (lane < nv) cid = indices[e0 + lane];
+      for (int64_t e0 = wk.beg; e0 < wk.end; e0 += WAVE) {
+        const Chunk ch = load_chunk<WAVE>(indices, nullptr, e0, wk.end, lane);
 #pragma unroll 4
-        for (int k = 0; k < nv; ++k) {
-          const int c = __shfl(cid, k, WAVE);
+        for (int k = 0; k < ch.nv; ++k) {
+          const int c = __shfl(ch.cid, k, WAVE);
           const int64_t we = wperm ? wperm[e0 + k] : (e0 + k);
           const int64_t base = (int64_t)c * HD4;
           if (hasA) f4_axpy(acc0, w[we * H + hA], x4[base + fA]);
           if (hasB) f4_axpy(acc1, w[we * H + hB], x4[base + fB]);
         }
       }
-      const int64_t ob = (int64_t)row * HD4;
-      if (atomic) {
-        if (hasA) {
-          float* p = reinterpret_cast<float*>(&out4[ob + fA]);
-          atomicAdd(p + 0, acc0.x); atomicAdd(p + 1, acc0.y);
-          atomicAdd(p + 2, acc0.z); atomicAdd(p + 3, acc0.w);
-        }
-        if (hasB) {
-          float* p = reinterpret_cast<float*>(&out4[ob + fB]);
-          atomicAdd(p + 0, acc1.x); atomicAdd(p + 1, acc1.y);
-          atomicAdd(p + 2, acc1.z); atomicAdd(p + 3, acc1.w);
-        }
-      } else if (ACC) {
-        if (hasA) {
-          float4 pv = out4[ob + fA];
-          pv.x += acc0.x; pv.y += acc0.y; pv.z += acc0.z; pv.w += acc0.w;
-          out4[ob + fA] = pv;
-        }
-        if (hasB) {
-          float4 pv = out4[ob + fB];
-          pv.x += acc1.x; pv.y += acc1.y; pv.z += acc1.z; pv.w += acc1.w;
-          out4[ob + fB] = pv;
-        }
-      } else {
-        if (hasA) out4[ob + fA] = acc0;
-        if (hasB) out4[ob + fB] = acc1;
-      }
+      const int64_t ob = (int64_t)wk.row * HD4;
+      if (hasA) store_row<ACC>(&out4[ob + fA], acc0, wk.atomic);
+      if (hasB) store_row<ACC>(&out4[ob + fB], acc1, wk.atomic);
     }
   }
 }
@@ -1201,28 +934,23 @@ __global__ __launch_bounds__(256) void sddmm_dot_vec4_kernel(
     const int32_t* __restrict__ indices, const float* __restrict__ g,
     const float* __restrict__ x, float* __restrict__ out, int H, int D,
     int HD) {
-  const int bb = xcd_remap_block(blockIdx.x, gridDim.x);
-  const int wv = bb * (blockDim.x / WAVE) + (threadIdx.x / WAVE);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int it_beg = wave_start[wv], it_end = wave_start[wv + 1];
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<WAVE>(wl);
+  const int lane = wi.lane;
   const int sg = lane >> 4;            // 4 subgroups of 16 lanes
   const int gl = lane & 15;
   const int D4 = D >> 2;
   const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
   const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
-  for (int it = it_beg; it < it_end; ++it) {
-    int row = wrow[it];
-    if (row < 0) row = ~row;
-    const int64_t beg = wbeg[it], end = wend[it];
-    const int64_t grow = (int64_t)row * (HD >> 2);
-    for (int64_t e0 = beg; e0 < end; e0 += WAVE) {
-      const int nv = (int)((end - e0 < WAVE) ? (end - e0) : WAVE);
-      int cid = 0;
-      if (lane < nv) cid = indices[e0 + lane];
-      for (int k0 = 0; k0 < nv; k0 += 4) {
+  for (int it = wi.beg; it < wi.end; ++it) {
+    const WorkItem wk = work_item(wl, it);
+    const int64_t grow = (int64_t)wk.row * (HD >> 2);
+    for (int64_t e0 = wk.beg; e0 < wk.end; e0 += WAVE) {
+      const Chunk ch = load_chunk<WAVE>(indices, nullptr, e0, wk.end, lane);
+      for (int k0 = 0; k0 < ch.nv; k0 += 4) {
         const int k = k0 + sg;
-        const bool act = k < nv;
-        const int c = __shfl(cid, act ? k : 0, WAVE);
+        const bool act = k < ch.nv;
+        const int c = __shfl(ch.cid, act ? k : 0, WAVE);
         const int64_t crow = (int64_t)c * (HD >> 2);
         for (int h = 0; h < H; ++h) {
           float p = 0.f;
@@ -1252,31 +980,27 @@ __global__ __launch_bounds__(256) void sddmm_dot_fast_kernel(
     const int32_t* __restrict__ indices, const float* __restrict__ g,
     const float* __restrict__ x, float* __restrict__ out, int H, int D,
     int HD) {
-  const int bb = xcd_remap_block(blockIdx.x, gridDim.x);
-  const int wv = bb * (blockDim.x / WAVE) + (threadIdx.x / WAVE);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int it_beg = wave_start[wv], it_end = wave_start[wv + 1];
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<WAVE>(wl);
+  const int lane = wi.lane;
   const int grp = D / 8;               // lanes per head group (pow2)
   const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
   const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
-  for (int it = it_beg; it < it_end; ++it) {
-    int row = wrow[it];
-    if (row < 0) row = ~row;           // no atomics needed: each (e,h) is
-    const int64_t beg = wbeg[it], end = wend[it];  // written exactly once
+  for (int it = wi.beg; it < wi.end; ++it) {
+    // split rows need no atomics: each (e,h) is written exactly once
+    const WorkItem wk = work_item(wl, it);
     const bool active = lane * 8 < HD;
     const int h = active ? (lane * 8) / D : 0;
     float4 rg0 = {0,0,0,0}, rg1 = {0,0,0,0};
     if (active) {
-      rg0 = g4[(int64_t)row * (HD / 4) + lane * 2];
-      rg1 = g4[(int64_t)row * (HD / 4) + lane * 2 + 1];
+      rg0 = g4[(int64_t)wk.row * (HD / 4) + lane * 2];
+      rg1 = g4[(int64_t)wk.row * (HD / 4) + lane * 2 + 1];
     }
-    for (int64_t e0 = beg; e0 < end; e0 += WAVE) {
-      const int nv = (int)((end - e0 < WAVE) ? (end - e0) : WAVE);
-      int cid = 0;
-      if (lane < nv) cid = indices[e0 + lane];
+    for (int64_t e0 = wk.beg; e0 < wk.end; e0 += WAVE) {
+      const Chunk ch = load_chunk<WAVE>(indices, nullptr, e0, wk.end, lane);
 #pragma unroll 2
-      for (int k = 0; k < nv; ++k) {
-        const int c = __shfl(cid, k, WAVE);
+      for (int k = 0; k < ch.nv; ++k) {
+        const int c = __shfl(ch.cid, k, WAVE);
         float p = 0.f;
         if (active) {
           const float4 xa = x4[(int64_t)c * (HD / 4) + lane * 2];
@@ -1303,31 +1027,24 @@ __global__ __launch_bounds__(256) void segment_sum_edges_kernel(
     const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
     const int64_t* __restrict__ perm, const float* __restrict__ grad,
     float* __restrict__ out, int H) {
-  const int bb = xcd_remap_block(blockIdx.x, gridDim.x);
-  const int wv = bb * (blockDim.x / WAVE) + (threadIdx.x / WAVE);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int it_beg = wave_start[wv], it_end = wave_start[wv + 1];
-  for (int it = it_beg; it < it_end; ++it) {
-    int row = wrow[it];
-    const bool atomic = row < 0;
-    if (atomic) row = ~row;
-    const int64_t beg = wbeg[it], end = wend[it];
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<WAVE>(wl);
+  for (int it = wi.beg; it < wi.end; ++it) {
+    const WorkItem wk = work_item(wl, it);
     // lane l accumulates head l%H over edges strided WAVE/H... simple:
     // each lane takes edges lane, lane+64, ... and adds all H into
     // per-lane partials, then wave-reduce per head.
     float acc[8];  // H <= 8 supported here (fallback in launcher)
 #pragma unroll
     for (int h = 0; h < 8; ++h) acc[h] = 0.f;
-    for (int64_t e = beg + lane; e < end; e += WAVE) {
+    for (int64_t e = wk.beg + wi.lane; e < wk.end; e += WAVE) {
       const int64_t ee = perm ? perm[e] : e;
       for (int h = 0; h < H; ++h) acc[h] += grad[ee * H + h];
     }
     for (int h = 0; h < H; ++h) {
       float v = wave_reduce_sum(acc[h]);
-      if (lane == 0) {
-        if (atomic) atomicAdd(&out[(int64_t)row * H + h], v);
-        else out[(int64_t)row * H + h] += v;
-      }
+      if (wi.lane == 0)
+        store_row<true>(&out[(int64_t)wk.row * H + h], v, wk.atomic);
     }
   }
 }
@@ -1338,32 +1055,19 @@ __global__ __launch_bounds__(256) void segment_sum_edges_h4_kernel(
     const int32_t* __restrict__ wrow, const int64_t* __restrict__ wbeg,
     const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
     const int64_t* __restrict__ perm, const float4* __restrict__ grad,
-    float* __restrict__ out) {
-  const int bb = xcd_remap_block(blockIdx.x, gridDim.x);
-  const int wv = bb * (blockDim.x / WAVE) + (threadIdx.x / WAVE);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int it_beg = wave_start[wv], it_end = wave_start[wv + 1];
-  for (int it = it_beg; it < it_end; ++it) {
-    int row = wrow[it];
-    const bool atomic = row < 0;
-    if (atomic) row = ~row;
-    const int64_t beg = wbeg[it], end = wend[it];
+    float4* __restrict__ out) {
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<WAVE>(wl);
+  for (int it = wi.beg; it < wi.end; ++it) {
+    const WorkItem wk = work_item(wl, it);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int64_t e = beg + lane; e < end; e += WAVE) {
+    for (int64_t e = wk.beg + wi.lane; e < wk.end; e += WAVE) {
       const int64_t ee = perm ? perm[e] : e;
       const float4 v = grad[ee];
       acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
     }
     acc = wave_reduce_sum4(acc);
-    if (lane == 0) {
-      float* o = &out[(int64_t)row * 4];
-      if (atomic) {
-        atomicAdd(o + 0, acc.x); atomicAdd(o + 1, acc.y);
-        atomicAdd(o + 2, acc.z); atomicAdd(o + 3, acc.w);
-      } else {
-        o[0] += acc.x; o[1] += acc.y; o[2] += acc.z; o[3] += acc.w;
-      }
-    }
+    if (wi.lane == 0) store_row<true>(&out[wk.row], acc, wk.atomic);
   }
 }
 
@@ -1743,12 +1447,7 @@ __global__ __launch_bounds__(256) void dropout_apply_v4_kernel(
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
        i += stride) {
     const float4 v = x[i];
-    float4 o;
-    o.x = (!drop || drop_keep(i * 4 + 0, thr, seed)) ? v.x * inv_keep : 0.f;
-    o.y = (!drop || drop_keep(i * 4 + 1, thr, seed)) ? v.y * inv_keep : 0.f;
-    o.z = (!drop || drop_keep(i * 4 + 2, thr, seed)) ? v.z * inv_keep : 0.f;
-    o.w = (!drop || drop_keep(i * 4 + 3, thr, seed)) ? v.w * inv_keep : 0.f;
-    out[i] = o;
+    out[i] = drop ? drop_apply(v, i * 4, thr, seed, inv_keep) : v;
   }
 }
 
@@ -1770,6 +1469,58 @@ int spmm_grid(int n_rows) {
   return std::min(blocks, 16384);
 }
 
+int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+// Host side of the work-list contract (common.h): the four schedule
+// arrays as built by ops/csr_torch.build_worklist, validated once for
+// every entry point. n_waves % 8 == 0 is what lets each launcher size
+// its grid as n_waves / (waves per 256-thread block) without a remainder
+// — a schedule that broke it would silently skip its last items.
+struct WorkListArgs {
+  WorkList wl;
+  int n_waves;
+};
+
+WorkListArgs worklist_args(const at::Tensor& wrow, const at::Tensor& wbeg,
+                           const at::Tensor& wend,
+                           const at::Tensor& wave_start) {
+  TORCH_CHECK(wrow.scalar_type() == at::kInt &&
+                  wbeg.scalar_type() == at::kLong &&
+                  wend.scalar_type() == at::kLong &&
+                  wave_start.scalar_type() == at::kInt,
+              "worklist: wrow/wave_start int32 and wbeg/wend int64 expected");
+  for (const at::Tensor* t : {&wrow, &wbeg, &wend, &wave_start})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                    t->device() == wave_start.device(),
+                "worklist arrays must be contiguous CUDA tensors on one "
+                "device");
+  // array-length consistency: the kernels index wbeg/wend by item id
+  TORCH_CHECK(wave_start.numel() >= 1 && wbeg.numel() == wrow.numel() &&
+                  wend.numel() == wrow.numel(),
+              "worklist: inconsistent array lengths (wrow ", wrow.numel(),
+              ", wbeg ", wbeg.numel(), ", wend ", wend.numel(),
+              ", wave_start ", wave_start.numel(), ")");
+  const int n_waves = (int)wave_start.numel() - 1;
+  TORCH_CHECK(n_waves % 8 == 0, "worklist: n_waves (", n_waves,
+              ") must be a multiple of 8");
+  return {{wrow.data_ptr<int32_t>(), wbeg.data_ptr<int64_t>(),
+           wend.data_ptr<int64_t>(), wave_start.data_ptr<int32_t>()},
+          n_waves};
+}
+
+// One work-list kernel launch: 256-thread blocks of 256 / subw waves (or
+// subgroups) each; the schedule pointers lead the argument list.
+template <typename K, typename... Args>
+void launch_worklist(K kernel, const WorkListArgs& w, int subw,
+                     Args... args) {
+  hipLaunchKernelGGL(kernel, dim3(w.n_waves / (256 / subw)), dim3(256), 0,
+                     at::cuda::getCurrentCUDAStream(), w.wl.row, w.wl.beg,
+                     w.wl.end, w.wl.wave_start, args...);
+}
+
 at::Tensor spmm_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
                     at::Tensor wave_start, at::Tensor indices, at::Tensor x,
                     c10::optional<at::Tensor> src_scale,
@@ -1780,80 +1531,35 @@ at::Tensor spmm_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
   // rows — ops/csr_torch.build_worklist zero_rows).
   check_f32(x, "x");
   check_f32(out, "out");
-  TORCH_CHECK(wrow.scalar_type() == at::kInt &&
-                  wbeg.scalar_type() == at::kLong &&
-                  wave_start.scalar_type() == at::kInt &&
-                  indices.scalar_type() == at::kInt,
-              "worklist int32/int64 + indices int32 expected");
+  TORCH_CHECK(indices.scalar_type() == at::kInt, "indices int32 expected");
+  const WorkListArgs wl = worklist_args(wrow, wbeg, wend, wave_start);
   const int F = x.size(1);
-  const int n_waves = wave_start.numel() - 1;
-  if (wrow.numel() == 0 || n_waves <= 0) return out;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  const int grid = n_waves / 4;
-  static const int strided_env = [] {
-    const char* e = getenv("BNSGCN_SPMM_STRIDED");
-    return e ? atoi(e) : 0;  // measured: strided LOSES ~1-6%
-    // (drifting waves break their own temporal locality; bench_strided_*)
-  }();
-  static const int subw32_max = [] {
-    const char* e = getenv("BNSGCN_SPMM_SUBW32_MAX");
-    return e ? atoi(e) : 32;  // f4 <= this runs the half-wave variant
-  }();
-  static const int narrow_max = [] {
-    const char* e = getenv("BNSGCN_SPMM_NARROW_MAX");
-    // f4 <= this runs the edge-parallel narrow kernel (0 disables it)
-    return std::min(e ? atoi(e) : 16, 16);
-  }();
-  if (F % 4 == 0) {
-    if (F / 4 <= std::min(narrow_max, subw32_max)) {
-      auto kfn = acc ? spmm_sum_narrow_kernel<true, 16>
-                     : spmm_sum_narrow_kernel<false, 16>;
-      hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), 0, stream,
-                         wrow.data_ptr<int32_t>(), wbeg.data_ptr<int64_t>(),
-                         wend.data_ptr<int64_t>(), wave_start.data_ptr<int32_t>(),
-                         indices.data_ptr<int32_t>(), x.data_ptr<float>(),
-                         opt_ptr(src_scale), opt_ptr(dst_scale),
-                         out.data_ptr<float>(), F / 4);
-      return out;
-    }
-    if (F / 4 <= subw32_max && n_waves % 8 == 0) {
-      const int strided = strided_env && (n_waves % 8 == 0);
-      auto kfn = acc ? spmm_sum_vec4_kernel<true, 32>
-                     : spmm_sum_vec4_kernel<false, 32>;
-      hipLaunchKernelGGL(kfn, dim3(n_waves / 8), dim3(256), 0, stream,
-                         wrow.data_ptr<int32_t>(), wbeg.data_ptr<int64_t>(),
-                         wend.data_ptr<int64_t>(), wave_start.data_ptr<int32_t>(),
-                         indices.data_ptr<int32_t>(), x.data_ptr<float>(),
-                         opt_ptr(src_scale), opt_ptr(dst_scale),
-                         out.data_ptr<float>(), F / 4, strided);
-      return out;
-    }
-    const int strided = strided_env && (n_waves % 8 == 0);
-    auto kfn = acc ? spmm_sum_vec4_kernel<true, 64>
-                   : spmm_sum_vec4_kernel<false, 64>;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), 0, stream,
-                       wrow.data_ptr<int32_t>(), wbeg.data_ptr<int64_t>(),
-                       wend.data_ptr<int64_t>(), wave_start.data_ptr<int32_t>(),
-                       indices.data_ptr<int32_t>(), x.data_ptr<float>(),
-                       opt_ptr(src_scale), opt_ptr(dst_scale),
-                       out.data_ptr<float>(), F / 4, strided);
-  } else if (F % 2 == 0) {
-    auto kfn = acc ? spmm_sum_vec2_kernel<true> : spmm_sum_vec2_kernel<false>;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), 0, stream,
-                       wrow.data_ptr<int32_t>(), wbeg.data_ptr<int64_t>(),
-                       wend.data_ptr<int64_t>(), wave_start.data_ptr<int32_t>(),
-                       indices.data_ptr<int32_t>(), x.data_ptr<float>(),
-                       opt_ptr(src_scale), opt_ptr(dst_scale),
-                       out.data_ptr<float>(), F / 2);
-  } else {
-    auto kfn = acc ? spmm_sum_scalar_kernel<true> : spmm_sum_scalar_kernel<false>;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), 0, stream,
-                       wrow.data_ptr<int32_t>(), wbeg.data_ptr<int64_t>(),
-                       wend.data_ptr<int64_t>(), wave_start.data_ptr<int32_t>(),
-                       indices.data_ptr<int32_t>(), x.data_ptr<float>(),
-                       opt_ptr(src_scale), opt_ptr(dst_scale),
-                       out.data_ptr<float>(), F);
-  }
+  if (wrow.numel() == 0 || wl.n_waves <= 0) return out;
+  // f4 <= this runs the half-wave variant
+  static const int subw32_max = env_int("BNSGCN_SPMM_SUBW32_MAX", 32);
+  // f4 <= this runs the edge-parallel narrow kernel (0 disables it)
+  static const int narrow_max =
+      std::min(env_int("BNSGCN_SPMM_NARROW_MAX", 16), 16);
+  auto launch = [&](auto kernel, int subw, int width) {
+    launch_worklist(kernel, wl, subw, indices.data_ptr<int32_t>(),
+                    x.data_ptr<float>(), opt_ptr(src_scale),
+                    opt_ptr(dst_scale), out.data_ptr<float>(), width);
+  };
+  if (F % 4 == 0 && F / 4 <= std::min(narrow_max, subw32_max))
+    launch(acc ? spmm_sum_narrow_kernel<true, 16>
+               : spmm_sum_narrow_kernel<false, 16>, 64, F / 4);
+  else if (F % 4 == 0 && F / 4 <= subw32_max)
+    launch(acc ? spmm_sum_vec4_kernel<true, 32>
+               : spmm_sum_vec4_kernel<false, 32>, 32, F / 4);
+  else if (F % 4 == 0)
+    launch(acc ? spmm_sum_vec4_kernel<true, 64>
+               : spmm_sum_vec4_kernel<false, 64>, 64, F / 4);
+  else if (F % 2 == 0)
+    launch(acc ? spmm_sum_vec2_kernel<true> : spmm_sum_vec2_kernel<false>,
+           64, F / 2);
+  else
+    launch(acc ? spmm_sum_scalar_kernel<true> : spmm_sum_scalar_kernel<false>,
+           64, F);
   return out;
 }
 
@@ -2031,17 +1737,13 @@ at::Tensor sddmm_add(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
                      at::Tensor wstart, at::Tensor indptr, at::Tensor indices,
                      at::Tensor el, at::Tensor er, double slope) {
   check_f32(el, "el"); check_f32(er, "er");
+  const WorkListArgs wl = worklist_args(wrow, wbeg, wend, wstart);
   const int H = el.size(1);
   auto out = at::empty({indices.numel(), H}, el.options());
-  const int n_waves = wstart.numel() - 1;
-  if (indices.numel() == 0 || n_waves <= 0) return out;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(sddmm_add_kernel, dim3(n_waves / 4), dim3(256), 0,
-                     stream, wrow.data_ptr<int32_t>(), wbeg.data_ptr<int64_t>(),
-                     wend.data_ptr<int64_t>(), wstart.data_ptr<int32_t>(),
-                     indices.data_ptr<int32_t>(), el.data_ptr<float>(),
-                     er.data_ptr<float>(), out.data_ptr<float>(), H,
-                     (float)slope);
+  if (indices.numel() == 0 || wl.n_waves <= 0) return out;
+  launch_worklist(sddmm_add_kernel, wl, 64, indices.data_ptr<int32_t>(),
+                  el.data_ptr<float>(), er.data_ptr<float>(),
+                  out.data_ptr<float>(), H, (float)slope);
   return out;
 }
 
@@ -2087,10 +1789,6 @@ std::vector<at::Tensor> segment_softmax2(at::Tensor ip1, at::Tensor l1,
   auto da2 = drop ? at::empty_like(l2) : a2;
   if (n_rows == 0) return {a1, a2, da1, da2};
   auto stream = at::cuda::getCurrentCUDAStream();
-  // interleaved variant: coalesced but consolidates per-(row,head) waves
-  // into per-row ones — measured SLOWER on Yelp GAT (85 -> 112 ms epoch;
-  // short power-law segments are latency-bound and lose the 4x head
-  // parallelism). Kept behind BNSGCN_SOFTMAX_ILV=1.
   if (H == 4) {   // float4-lane form: coalesced, same pass structure
     // short power-law segments are latency-bound: give each wave as few
     // serial rows as possible (the 16384-block worklist cap left ~11
@@ -2107,21 +1805,6 @@ std::vector<at::Tensor> segment_softmax2(at::Tensor ip1, at::Tensor l1,
                        reinterpret_cast<float4*>(da1.data_ptr<float>()),
                        reinterpret_cast<float4*>(da2.data_ptr<float>()),
                        n_rows, (float)keep, (uint64_t)seed, l1.numel());
-    return {a1, a2, da1, da2};
-  }
-  static const int ilv_env = [] {
-    const char* e = getenv("BNSGCN_SOFTMAX_ILV");
-    return e ? atoi(e) : 0;
-  }();
-  const bool pow2 = ilv_env && H <= 32 && (H & (H - 1)) == 0;
-  if (pow2) {
-    hipLaunchKernelGGL(segment_softmax2_ilv_kernel,
-                       dim3(spmm_grid(n_rows)), dim3(256), 0, stream,
-                       ip1.data_ptr<int64_t>(), l1.data_ptr<float>(),
-                       ip2.data_ptr<int64_t>(), l2.data_ptr<float>(),
-                       a1.data_ptr<float>(), a2.data_ptr<float>(),
-                       da1.data_ptr<float>(), da2.data_ptr<float>(),
-                       n_rows, H, (float)keep, (uint64_t)seed, l1.numel());
     return {a1, a2, da1, da2};
   }
   hipLaunchKernelGGL(segment_softmax2_kernel, dim3(spmm_grid(n_rows * H)),
@@ -2159,21 +1842,6 @@ std::vector<at::Tensor> segment_softmax2_backward(at::Tensor ip1, at::Tensor a1,
                        n_rows, (float)keep, (uint64_t)seed, a1.numel());
     return {d1, d2};
   }
-  static const int ilv_env = [] {
-    const char* e = getenv("BNSGCN_SOFTMAX_ILV");
-    return e ? atoi(e) : 0;
-  }();
-  const bool pow2 = ilv_env && H <= 32 && (H & (H - 1)) == 0;
-  if (pow2) {
-    hipLaunchKernelGGL(segment_softmax2_ilv_bwd_kernel,
-                       dim3(spmm_grid(n_rows)), dim3(256), 0, stream,
-                       ip1.data_ptr<int64_t>(), a1.data_ptr<float>(),
-                       g1.data_ptr<float>(), ip2.data_ptr<int64_t>(),
-                       a2.data_ptr<float>(), g2.data_ptr<float>(),
-                       d1.data_ptr<float>(), d2.data_ptr<float>(),
-                       n_rows, H, (float)keep, (uint64_t)seed, a1.numel());
-    return {d1, d2};
-  }
   hipLaunchKernelGGL(segment_softmax2_bwd_kernel, dim3(spmm_grid(n_rows * H)),
                      dim3(256), 0, stream, ip1.data_ptr<int64_t>(),
                      a1.data_ptr<float>(), g1.data_ptr<float>(),
@@ -2191,24 +1859,21 @@ at::Tensor spmm_edge_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
                          at::Tensor out, bool acc) {
   // out is caller-allocated (split/empty rows pre-zeroed — see spmm_sum)
   check_f32(w, "w"); check_f32(x, "x"); check_f32(out, "out");
+  const WorkListArgs wl = worklist_args(wrow, wbeg, wend, wstart);
   const int n_rows = indptr.numel() - 1;
   const int H = x.size(1), D = x.size(2);
   if (indices.numel() == 0 || n_rows == 0) return out;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  const int n_waves = wstart.numel() - 1;
-  if (D % 4 == 0 && n_waves > 0) {
-    auto kfn = acc ? spmm_edge_vec4_kernel<true> : spmm_edge_vec4_kernel<false>;
-    hipLaunchKernelGGL(kfn, dim3(n_waves / 4), dim3(256), 0, stream,
-                       wrow.data_ptr<int32_t>(), wbeg.data_ptr<int64_t>(),
-                       wend.data_ptr<int64_t>(), wstart.data_ptr<int32_t>(),
-                       indices.data_ptr<int32_t>(), w.data_ptr<float>(),
-                       wperm.has_value() ? wperm->data_ptr<int64_t>() : nullptr,
-                       x.data_ptr<float>(), out.data_ptr<float>(), H, D / 4,
-                       H * D / 4);
+  if (D % 4 == 0 && wl.n_waves > 0) {
+    launch_worklist(acc ? spmm_edge_vec4_kernel<true>
+                        : spmm_edge_vec4_kernel<false>,
+                    wl, 64, indices.data_ptr<int32_t>(), w.data_ptr<float>(),
+                    wperm.has_value() ? wperm->data_ptr<int64_t>() : nullptr,
+                    x.data_ptr<float>(), out.data_ptr<float>(), H, D / 4,
+                    H * D / 4);
     return out;
   }
-  at::Tensor wp = wperm.has_value() ? w.index_select(0, *wperm) : w;
-  w = wp;
+  if (wperm.has_value()) w = w.index_select(0, *wperm);
+  auto stream = at::cuda::getCurrentCUDAStream();
   auto kfn = acc ? spmm_edge_kernel<true> : spmm_edge_kernel<false>;
   hipLaunchKernelGGL(kfn, dim3(spmm_grid(n_rows * H)), dim3(256), 0, stream,
                      indptr.data_ptr<int64_t>(), indices.data_ptr<int32_t>(),
@@ -2221,39 +1886,19 @@ at::Tensor sddmm_dot(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
                      at::Tensor wstart, at::Tensor indptr, at::Tensor indices,
                      at::Tensor g, at::Tensor x) {
   check_f32(g, "g"); check_f32(x, "x");
-  const int n_rows = indptr.numel() - 1;
+  const WorkListArgs wl = worklist_args(wrow, wbeg, wend, wstart);
   const int H = x.size(1), D = x.size(2);
   const int HD = H * D;
   auto out = at::empty({indices.numel(), H}, x.options());
-  if (indices.numel() == 0) return out;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  const int n_waves = wstart.numel() - 1;
+  if (indices.numel() == 0 || wl.n_waves <= 0) return out;
   const int grp = D / 8;
   const bool fast = HD <= 512 && D % 8 == 0 && grp > 0 &&
-                    (grp & (grp - 1)) == 0 && n_waves > 0;
-  if (fast) {
-    hipLaunchKernelGGL(sddmm_dot_fast_kernel, dim3(n_waves / 4), dim3(256), 0,
-                       stream, wrow.data_ptr<int32_t>(),
-                       wbeg.data_ptr<int64_t>(), wend.data_ptr<int64_t>(),
-                       wstart.data_ptr<int32_t>(), indices.data_ptr<int32_t>(),
-                       g.data_ptr<float>(), x.data_ptr<float>(),
-                       out.data_ptr<float>(), H, D, HD);
-    return out;
-  }
-  if (D % 4 == 0) {
-    hipLaunchKernelGGL(sddmm_dot_vec4_kernel, dim3(n_waves / 4), dim3(256),
-                       0, stream, wrow.data_ptr<int32_t>(),
-                       wbeg.data_ptr<int64_t>(), wend.data_ptr<int64_t>(),
-                       wstart.data_ptr<int32_t>(), indices.data_ptr<int32_t>(),
-                       g.data_ptr<float>(), x.data_ptr<float>(),
-                       out.data_ptr<float>(), H, D, H * D);
-    return out;
-  }
-  hipLaunchKernelGGL(sddmm_dot_gen_kernel, dim3(n_waves / 4), dim3(256), 0,
-                     stream, wrow.data_ptr<int32_t>(), wbeg.data_ptr<int64_t>(),
-                     wend.data_ptr<int64_t>(), wstart.data_ptr<int32_t>(),
-                     indices.data_ptr<int32_t>(), g.data_ptr<float>(),
-                     x.data_ptr<float>(), out.data_ptr<float>(), H, D, H * D);
+                    (grp & (grp - 1)) == 0;
+  launch_worklist(fast ? sddmm_dot_fast_kernel
+                       : D % 4 == 0 ? sddmm_dot_vec4_kernel
+                                    : sddmm_dot_gen_kernel,
+                  wl, 64, indices.data_ptr<int32_t>(), g.data_ptr<float>(),
+                  x.data_ptr<float>(), out.data_ptr<float>(), H, D, HD);
   return out;
 }
 
@@ -2264,25 +1909,17 @@ at::Tensor segment_sum_edges(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
   check_f32(grad, "grad");
   const int H = grad.size(1);
   TORCH_CHECK(H <= 8, "segment_sum_edges supports H <= 8");
+  const WorkListArgs wl = worklist_args(wrow, wbeg, wend, wstart);
   auto out = at::zeros({n_rows, H}, grad.options());
-  const int n_waves = wstart.numel() - 1;
-  if (n_waves <= 0 || wrow.numel() == 0) return out;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  if (H == 4) {
-    hipLaunchKernelGGL(segment_sum_edges_h4_kernel, dim3(n_waves / 4),
-                       dim3(256), 0, stream, wrow.data_ptr<int32_t>(),
-                       wbeg.data_ptr<int64_t>(), wend.data_ptr<int64_t>(),
-                       wstart.data_ptr<int32_t>(),
-                       perm.has_value() ? perm->data_ptr<int64_t>() : nullptr,
-                       reinterpret_cast<const float4*>(grad.data_ptr<float>()),
-                       out.data_ptr<float>());
-    return out;
-  }
-  hipLaunchKernelGGL(segment_sum_edges_kernel, dim3(n_waves / 4), dim3(256), 0,
-                     stream, wrow.data_ptr<int32_t>(), wbeg.data_ptr<int64_t>(),
-                     wend.data_ptr<int64_t>(), wstart.data_ptr<int32_t>(),
-                     perm.has_value() ? perm->data_ptr<int64_t>() : nullptr,
-                     grad.data_ptr<float>(), out.data_ptr<float>(), H);
+  if (wl.n_waves <= 0 || wrow.numel() == 0) return out;
+  const int64_t* pp = perm.has_value() ? perm->data_ptr<int64_t>() : nullptr;
+  if (H == 4)
+    launch_worklist(segment_sum_edges_h4_kernel, wl, 64, pp,
+                    reinterpret_cast<const float4*>(grad.data_ptr<float>()),
+                    reinterpret_cast<float4*>(out.data_ptr<float>()));
+  else
+    launch_worklist(segment_sum_edges_kernel, wl, 64, pp,
+                    grad.data_ptr<float>(), out.data_ptr<float>(), H);
   return out;
 }
 
@@ -2366,7 +2003,6 @@ at::Tensor gemm_strided(const at::Tensor& A, int64_t sAm, int64_t sAk,
     return C;
   }
   auto C = at::empty({M, N}, A.options());
-  if (M == 0 || N == 0) return C;
   hipLaunchKernelGGL(gemm_f32_kernel<false>, grid, dim3(256), 0, stream,
                      A.data_ptr<float>(), sAm, sAk, B.data_ptr<float>(), sBk,
                      sBn, opt_ptr(bias), C.data_ptr<float>(), M, N, K, K);

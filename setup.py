@@ -17,6 +17,7 @@ setup(
         CUDAExtension(
             "bnsgcn_amd._C",
             sources=["bnsgcn_amd/ops/hip/kernels.hip"],
+            depends=["bnsgcn_amd/ops/hip/common.h"],
             extra_compile_args={"nvcc": ["-O3"], "cxx": ["-O3"]},
         )
     ],

@@ -616,10 +616,9 @@ def check_softmax_wrapped(n_rows, H):
 
 def check_softmax2_wrapped(n_rows, H, form):
     """Union softmax + backward beyond the first pass of the grid of the
-    kernel form that H (and BNSGCN_SOFTMAX_ILV) selects: 'general' is a
-    wave per (row, head) on 65,536 waves, 'ilv' a wave per row on 65,536,
-    'h4' a wave per row on 262,144."""
-    items, waves = {"general": (n_rows * H, 65536), "ilv": (n_rows, 65536),
+    kernel form that H selects: 'general' is a wave per (row, head) on
+    65,536 waves, 'h4' a wave per row on 262,144."""
+    items, waves = {"general": (n_rows * H, 65536),
                     "h4": (n_rows, 262144)}[form]
     assert items > waves and (form == "h4") == (H == 4)
     from bnsgcn_amd.ops.functional import (segment_softmax2_raw,

@@ -397,26 +397,6 @@ def check_softmax2_dropout(H, keep=0.7):
 
 # ---------------------------------------------------------- script mode
 
-def _case_softmax_ilv():
-    assert os.environ.get("BNSGCN_SOFTMAX_ILV") == "1"
-    for H in (1, 2, 8, 16, 32):
-        check_softmax2(H)
-    check_softmax2_dropout(8)
-    # explicit seed: the interleaved kernel draws the host mask too, and
-    # its row loop wraps (66,000 rows > 65,536 waves)
-    import dense_path_checks as D
-    D.check_softmax2_dropout_seeded(8)
-    D.check_softmax2_keep_rounds_to_one(8)
-    D.check_softmax2_wrapped(66000, 8, "ilv")
-
-
-def _case_spmm_strided():
-    assert os.environ.get("BNSGCN_SPMM_STRIDED") == "1"
-    for F in (128, 256):
-        for scales, acc in ((True, False), (False, False), (False, True)):
-            check_spmm_sum(F, scales, acc)
-
-
 def _case_spmm_subw64():
     assert os.environ.get("BNSGCN_SPMM_SUBW32_MAX") == "0"
     for F in (64, 128):
@@ -426,8 +406,6 @@ def _case_spmm_subw64():
 
 # case name -> (environment switch, runner)
 CASES = {
-    "softmax_ilv": ({"BNSGCN_SOFTMAX_ILV": "1"}, _case_softmax_ilv),
-    "spmm_strided": ({"BNSGCN_SPMM_STRIDED": "1"}, _case_spmm_strided),
     "spmm_subw64": ({"BNSGCN_SPMM_SUBW32_MAX": "0"}, _case_spmm_subw64),
 }
 

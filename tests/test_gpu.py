@@ -616,8 +616,7 @@ def test_train_and_eval_on_gpu_accuracy():
 
 
 @needs_gpu
-# H == 4 -> float4 kernel, every other H -> general kernel (the interleaved
-# pow2 kernel only runs under BNSGCN_SOFTMAX_ILV=1: test_gpu_kernel_paths.py)
+# H == 4 -> float4 kernel, every other H -> general kernel
 @pytest.mark.parametrize("H", [4, 3, 1, 16])
 def test_segment_softmax2_matches_reference(H):
     from bnsgcn_amd.ops.functional import segment_softmax2_raw

@@ -225,16 +225,15 @@ def test_dropout_p_one_gives_zeros(n):
 # ---------------------------------------------- fused attention dropout
 
 @needs_gpu
-@pytest.mark.parametrize("H", [4, 3])
+@pytest.mark.parametrize("H", [4, 3, 8])
 def test_fused_attn_dropout_mask_matches_host(H):
-    """float4 (H = 4) and general (H = 3) kernels; the interleaved one
-    (H = 8) runs in test_env_gated_variants_in_child_processes."""
+    """float4 (H = 4) and general (H = 3, 8) kernels."""
     D.check_softmax2_dropout_seeded(H)
     D.check_softmax2_dropout_seeded(H, keep=0.5, seed=2**62 - 1)
 
 
 @needs_gpu
-@pytest.mark.parametrize("H", [4, 3])
+@pytest.mark.parametrize("H", [4, 3, 8])
 def test_fused_attn_dropout_keep_rounds_to_one(H):
     """keep = 1 - 1e-9 is below 1 as a double and 1.0f in the kernel: the
     launcher must not hand out separate da1/da2 that no kernel writes."""
@@ -281,6 +280,7 @@ def test_segment_softmax_wrapped():
 
 @needs_gpu
 @pytest.mark.parametrize("n_rows,H,form", [(22000, 3, "general"),
+                                           (8200, 8, "general"),
                                            (262150, 4, "h4")])
 def test_segment_softmax2_wrapped(n_rows, H, form):
     D.check_softmax2_wrapped(n_rows, H, form)

@@ -102,11 +102,12 @@ def test_segment_sum_edges_fixture(H):
 # -------------------------------------------------------- union softmax
 
 @needs_gpu
-@pytest.mark.parametrize("H", [4, 3, 1, 8])
+@pytest.mark.parametrize("H", [4, 3, 1, 8, 16, 32])
 def test_segment_softmax2_shifted(H):
     """Union softmax + backward on two long-segment edge sets whose
     logits differ by +-90 per row: only the max over BOTH sets keeps
-    fp32 exp finite."""
+    fp32 exp finite. H = 4 is the float4 kernel, every other H the
+    wave-per-(row, head) one."""
     K.check_softmax2(H)
 
 
@@ -350,14 +351,49 @@ def test_gemm_k_below_tile():
                        gd.abs().t() @ xd.abs(), float(M), "gemm_tn K=5")
 
 
+# ------------------------------------------- work-list host-side check
+
+@needs_gpu
+def test_worklist_entry_points_reject_12_waves():
+    """Every work-list entry point sizes its grid as n_waves / (waves per
+    block), so a wave_start of 13 entries (12 waves, not a multiple of 8)
+    must raise on the host before anything is launched. The 12-wave
+    schedule itself is well formed (monotone, ends at the item count)."""
+    from bnsgcn_amd.ops.csr_torch import build_worklist
+    n, H, D = 20, 4, 8
+    rng = np.random.default_rng(1300)
+    ip, ix = K._csr_from_degrees(rng.integers(0, 6, n), n, rng)
+    ip, ix = cu(ip), cu(ix)
+    wrow, wbeg, wend, wstart, _ = build_worklist(ip)
+    assert (wstart.numel() - 1) % 8 == 0
+    bad = torch.linspace(0, wrow.numel(), 13).to(torch.int32).to(DEV)
+    assert bad.numel() == 13 and int(bad[-1]) == wrow.numel()
+    wl = (wrow, wbeg, wend, bad)
+    E = ix.numel()
+    x2 = torch.randn(n, D, device=DEV)
+    x3 = torch.randn(n, H, D, device=DEV)
+    eh = torch.randn(E, H, device=DEV)
+    nh = torch.randn(n, H, device=DEV)
+    calls = {
+        "spmm_sum": lambda: ext.spmm_sum(*wl, ix, x2, None, None,
+                                         torch.zeros_like(x2), False),
+        "sddmm_add": lambda: ext.sddmm_add(*wl, ip, ix, nh, nh, 0.2),
+        "spmm_edge_sum": lambda: ext.spmm_edge_sum(
+            *wl, ip, ix, eh, None, x3, torch.zeros_like(x3), False),
+        "sddmm_dot": lambda: ext.sddmm_dot(*wl, ip, ix, x3, x3),
+        "segment_sum_edges": lambda: ext.segment_sum_edges(*wl, None, eh, n),
+    }
+    for name, call in calls.items():
+        with pytest.raises(RuntimeError, match="multiple of 8"):
+            call()
+    torch.cuda.synchronize()
+
+
 # ------------------------------------- environment-gated kernel variants
 
 @needs_gpu
 def test_env_gated_variants_in_child_processes():
-    """BNSGCN_SOFTMAX_ILV=1 (interleaved union softmax, H in {1,2,8,16,32},
-    forward/backward with the +-90 shifts and one dropout case),
-    BNSGCN_SPMM_STRIDED=1 (strided item walk, F in {128,256}) and
-    BNSGCN_SPMM_SUBW32_MAX=0 (narrow F through the 64-wide kernel, F in
+    """BNSGCN_SPMM_SUBW32_MAX=0 (narrow F through the 64-wide kernel, F in
     {64,128}). The extension reads each switch once per process, so every
     variant runs in a fresh child — one at a time, and none is started
     after one that failed, timed out or died on a signal."""
