@@ -280,11 +280,20 @@ def segment_softmax(logits, indptr):
 
 import os as _os
 
-# GEMM dispatch (K6). Per-shape A/B on MI355X (profiles/gemm_micro_r02):
-# rocBLAS wins the NT forward and NN dx by 1.5-2x on the tall-skinny
-# bench shapes; OUR split-K MFMA gemm_tn wins the dW reduction by up to
-# 3x (rocBLAS is weak at K >> M=N). "auto" routes each direction to the
-# winner; BNSGCN_GEMM=hip forces the hand-written kernels everywhere.
+# GEMM dispatch (K6). Two hand-written fp32 MFMA kernels live behind
+# gemm_nt_bias / gemm_nn / gemm_tn: the 64x64 gemm_f32_kernel and the tiled
+# 128x128 kernel (ops/hip/gemm_tiled.hip); the extension routes between
+# them by shape and alignment (kernels.hip route_tiled). Per-shape A/B on
+# MI355X (profiles/BENCH_SUMMARY_gemm_tiled.md), ms, rocBLAS / tiled / 64x64:
+#   NT forward [232965,1204]x[256,1204]^T  1.33 / 1.54 / 2.04  -> rocBLAS
+#   NT forward [232965, 256]x[256, 256]^T  0.28 / 0.38 / 0.47  -> rocBLAS
+#   NN dx      [232965, 256]x[256, 256]    0.33 / 0.32 / 0.44  -> rocBLAS
+#     (a 3 % kernel-level gap, 0.02 ms per epoch: not moved)
+#   TN dW      [232965,256]^T x [232965,1204]  1.83 / 1.41 / 2.06 -> tiled
+#     and every other aligned dW (0.34 against 0.73 / 0.43 at 256x256);
+#     41/44-wide outputs stay on the 64x64 kernel.
+# "auto" routes each direction to the winner; BNSGCN_GEMM=hip forces the
+# hand-written kernels everywhere.
 _GEMM_MODE = _os.environ.get("BNSGCN_GEMM", "auto")
 
 
@@ -325,6 +334,54 @@ class _Linear(Function):
 
 def linear(x, weight, bias=None):
     return _Linear.apply(x, weight, bias)
+
+
+class _DropoutLinear(Function):
+    """dropout(x) W^T + b with the dropout fused into the tiled GEMM's
+    operand load, forward and dW: x itself is saved, the mask is
+    regenerated from (seed, flat index) in backward, and the dropped-out
+    copy of x never exists. x gets no gradient (the caller guarantees it
+    needs none)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, keep, seed):
+        x = x.contiguous()
+        ctx.save_for_backward(x, weight)
+        ctx.keep, ctx.seed = keep, seed
+        ctx.has_bias = bias is not None
+        return get_ext().gemm_nt_bias_drop(x, weight.contiguous(), bias,
+                                           keep, seed)
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, weight = ctx.saved_tensors
+        grad = grad.contiguous()
+        e = get_ext()
+        gw = gb = None
+        if ctx.needs_input_grad[1]:
+            gw = e.gemm_tn_drop(grad, x, ctx.keep, ctx.seed)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            gb = e.syncbn_stats(grad)[0]
+        return None, gw, gb, None, None
+
+
+def dropout_linear(x, weight, bias, p: float, training: bool):
+    """linear(dropout(x, p, training), weight, bias). On the GPU, for an
+    fp32 x that needs no gradient, the dropout is applied inside the GEMMs
+    (_DropoutLinear); the seed is drawn exactly as dropout() draws it, so
+    masks are those of the unfused path. Everything else — CPU tensors,
+    x.requires_grad, p <= 0, eval — is the unfused composition.
+
+    A memory lever, not a speed one: it saves the dropped-out copy of x
+    (1.12 GB for the headline layer-0 input) but recomputes the splitmix64
+    mask once per output tile column, and the Reddit epoch measured 0.38 ms
+    slower with it than with dropout() + rocBLAS
+    (profiles/BENCH_SUMMARY_gemm_tiled.md) — the models do not call it."""
+    if (training and p > 0.0 and use_hip(x) and x.dtype == torch.float32
+            and not x.requires_grad):
+        seed = int(torch.randint(0, 2**62, (1,)).item())
+        return _DropoutLinear.apply(x, weight, bias, 1.0 - p, seed)
+    return linear(dropout(x, p, training), weight, bias)
 
 
 class _BiasAdd(Function):

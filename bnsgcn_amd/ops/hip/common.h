@@ -143,3 +143,44 @@ DEV_INLINE P4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
   }
   return {c0, c1, c2, c3};
 }
+
+// --------------------------------------------------------------- dropout
+// Dropout mask (attention dropout fused into the union softmax, feature
+// dropout, and the dropout fused into the tiled GEMM's operand staging —
+// kernels.hip, gemm_tiled.hip): element idx keeps its value iff splitmix64(seed + idx) high bits < keep * 2^32. The mask is
+// REGENERATED in backward from (seed, idx) — never stored. splitmix64
+// (~8 ALU ops) instead of Philox4x32-10: the softmax kernel is
+// latency-bound over short segments and the 10-round Philox measured
+// +1.6 ms on the Yelp GAT backward (profiles/topk_gat2_r02.txt).
+DEV_INLINE bool drop_keep(int64_t idx, uint32_t thr, uint64_t seed) {
+  uint64_t z = seed + (uint64_t)idx;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (uint32_t)(z >> 32) < thr;
+}
+
+// `keep` reaches every kernel as a float, and dropout is active iff THAT
+// float is below 1: a double just under 1 rounds to exactly 1.0f, and
+// 1.0f * 2^32 does not fit a uint32_t (the conversion is undefined). The
+// launchers decide on the same rounded value, so the kernels and the
+// allocation of da1/da2 cannot disagree. keep <= 0 drops everything.
+DEV_INLINE uint32_t drop_threshold(float keep) {
+  return (keep > 0.f && keep < 1.0f)
+             ? (uint32_t)((double)keep * 4294967296.0) : 0u;
+}
+
+// Dropout of one value / one float4 whose first component has flat mask
+// index idx: kept elements are scaled by 1/keep, dropped ones are 0.
+DEV_INLINE float drop_apply(float v, int64_t idx, uint32_t thr, uint64_t seed,
+                            float inv_keep) {
+  return drop_keep(idx, thr, seed) ? v * inv_keep : 0.f;
+}
+
+DEV_INLINE float4 drop_apply(float4 v, int64_t idx, uint32_t thr,
+                             uint64_t seed, float inv_keep) {
+  return make_float4(drop_apply(v.x, idx + 0, thr, seed, inv_keep),
+                     drop_apply(v.y, idx + 1, thr, seed, inv_keep),
+                     drop_apply(v.z, idx + 2, thr, seed, inv_keep),
+                     drop_apply(v.w, idx + 3, thr, seed, inv_keep));
+}

@@ -11,6 +11,7 @@
 #include <c10/util/Optional.h>
 #include <algorithm>
 #include "common.h"
+#include "gemm_tiled.h"
 
 namespace {
 
@@ -531,44 +532,7 @@ __global__ void segment_softmax_bwd_kernel(const int64_t* __restrict__ indptr,
 
 // Union softmax over TWO per-row edge segments (split GAT block:
 // static inner edges + per-epoch sampled halo edges) — shared max/sum.
-// Dropout mask for fused attention dropout: element idx keeps its value
-// iff splitmix64(seed + idx) high bits < keep * 2^32. The mask is
-// REGENERATED in backward from (seed, idx) — never stored. splitmix64
-// (~8 ALU ops) instead of Philox4x32-10: the softmax kernel is
-// latency-bound over short segments and the 10-round Philox measured
-// +1.6 ms on the Yelp GAT backward (profiles/topk_gat2_r02.txt).
-DEV_INLINE bool drop_keep(int64_t idx, uint32_t thr, uint64_t seed) {
-  uint64_t z = seed + (uint64_t)idx;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (uint32_t)(z >> 32) < thr;
-}
-
-// `keep` reaches every kernel as a float, and dropout is active iff THAT
-// float is below 1: a double just under 1 rounds to exactly 1.0f, and
-// 1.0f * 2^32 does not fit a uint32_t (the conversion is undefined). The
-// launchers decide on the same rounded value, so the kernels and the
-// allocation of da1/da2 cannot disagree. keep <= 0 drops everything.
-DEV_INLINE uint32_t drop_threshold(float keep) {
-  return (keep > 0.f && keep < 1.0f)
-             ? (uint32_t)((double)keep * 4294967296.0) : 0u;
-}
-
-// Dropout of one value / one float4 whose first component has flat mask
-// index idx: kept elements are scaled by 1/keep, dropped ones are 0.
-DEV_INLINE float drop_apply(float v, int64_t idx, uint32_t thr, uint64_t seed,
-                            float inv_keep) {
-  return drop_keep(idx, thr, seed) ? v * inv_keep : 0.f;
-}
-
-DEV_INLINE float4 drop_apply(float4 v, int64_t idx, uint32_t thr,
-                             uint64_t seed, float inv_keep) {
-  return make_float4(drop_apply(v.x, idx + 0, thr, seed, inv_keep),
-                     drop_apply(v.y, idx + 1, thr, seed, inv_keep),
-                     drop_apply(v.z, idx + 2, thr, seed, inv_keep),
-                     drop_apply(v.w, idx + 3, thr, seed, inv_keep));
-}
+// The fused attention dropout uses the mask of common.h (drop_keep).
 
 DEV_INLINE float4 f4_max(float4 a, float4 b) {
   return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z),
@@ -2009,27 +1973,84 @@ at::Tensor gemm_strided(const at::Tensor& A, int64_t sAm, int64_t sAk,
   return C;
 }
 
+// Kernel choice of the three public GEMMs. `kernel`: GEMM_AUTO routes by
+// shape, GEMM_OLD / GEMM_TILED force gemm_f32_kernel / the tiled kernel
+// (gemm_tiled.hip) at any shape — for tests and A/B timing.
+// Auto takes the tiled kernel when its float4 staging applies (16-byte
+// aligned rows) and its 128x128 tile pads the output no more than 25 %
+// beyond what the 64x64 tile does: 41-wide or K % 4 != 0 operands and
+// small or narrow outputs (N = 44 pads to 128 against 64) stay on
+// gemm_f32_kernel.
+enum { GEMM_AUTO = 0, GEMM_OLD = 1, GEMM_TILED = 2 };
+
+bool route_tiled(bns::GemmLayout layout, const at::Tensor& A,
+                 const at::Tensor& B, int M, int N, int R, int64_t kernel) {
+  TORCH_CHECK(kernel >= GEMM_AUTO && kernel <= GEMM_TILED, "bad kernel id");
+  if (kernel == GEMM_OLD || M == 0 || N == 0 || R == 0) return false;
+  if (kernel == GEMM_TILED) return true;
+  if (!bns::gemm_tiled_aligned(layout, A, B, M, N, R) || R < 32) return false;
+  auto pad = [](int64_t v, int64_t t) { return (v + t - 1) / t * t; };
+  return 4 * pad(M, 128) * pad(N, 128) <= 5 * pad(M, BM) * pad(N, BN);
+}
+
 // y[M,N] = x[M,K] @ w[N,K]^T + b
 at::Tensor gemm_nt_bias(at::Tensor x, at::Tensor w,
-                        c10::optional<at::Tensor> bias) {
+                        c10::optional<at::Tensor> bias, int64_t kernel) {
   check_f32(x, "x"); check_f32(w, "w");
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K, "shape mismatch");
+  if (route_tiled(bns::GEMM_NT, x, w, M, N, K, kernel))
+    return bns::gemm_tiled(bns::GEMM_NT, x, w, bias, M, N, K);
   return gemm_strided(x, K, 1, w, 1, K, bias, M, N, K);
 }
 
 // dx[M,K] = g[M,N] @ w[N,K]
-at::Tensor gemm_nn(at::Tensor g, at::Tensor w) {
+at::Tensor gemm_nn(at::Tensor g, at::Tensor w, int64_t kernel) {
   check_f32(g, "g"); check_f32(w, "w");
   const int M = g.size(0), N = g.size(1), K = w.size(1);
+  TORCH_CHECK(w.size(0) == N, "shape mismatch");
+  if (route_tiled(bns::GEMM_NN, g, w, M, K, N, kernel))
+    return bns::gemm_tiled(bns::GEMM_NN, g, w, c10::nullopt, M, K, N);
   return gemm_strided(g, N, 1, w, K, 1, c10::nullopt, M, K, N);
 }
 
 // dw[N,K] = g[M,N]^T @ x[M,K]
-at::Tensor gemm_tn(at::Tensor g, at::Tensor x) {
+at::Tensor gemm_tn(at::Tensor g, at::Tensor x, int64_t kernel) {
   check_f32(g, "g"); check_f32(x, "x");
   const int M = g.size(0), N = g.size(1), K = x.size(1);
+  TORCH_CHECK(x.size(0) == M, "shape mismatch");
+  if (route_tiled(bns::GEMM_TN, g, x, N, K, M, kernel))
+    return bns::gemm_tiled(bns::GEMM_TN, g, x, c10::nullopt, N, K, M);
   return gemm_strided(g, 1, N, x, K, 1, c10::nullopt, N, K, M);
+}
+
+// Dropout fused into the activation operand (tiled kernel only): the
+// operand x is read as drop_apply(x[m, k], m*K + k, ...) while it is
+// staged — the values entering the MFMAs are bit-identical to
+// dropout_apply(x, keep, seed), which is never materialized.
+// y[M,N] = dropout(x)[M,K] @ w[N,K]^T + b
+at::Tensor gemm_nt_bias_drop(at::Tensor x, at::Tensor w,
+                             c10::optional<at::Tensor> bias, double keep,
+                             int64_t seed) {
+  check_f32(x, "x"); check_f32(w, "w");
+  const int M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(w.size(1) == K, "shape mismatch");
+  if (M == 0 || N == 0 || K == 0)
+    return gemm_strided(x, K, 1, w, 1, K, bias, M, N, K);
+  return bns::gemm_tiled(bns::GEMM_NT, x, w, bias, M, N, K, bns::DROP_A,
+                         (float)keep, (uint64_t)seed);
+}
+
+// dw[N,K] = g[M,N]^T @ dropout(x)[M,K]
+at::Tensor gemm_tn_drop(at::Tensor g, at::Tensor x, double keep,
+                        int64_t seed) {
+  check_f32(g, "g"); check_f32(x, "x");
+  const int M = g.size(0), N = g.size(1), K = x.size(1);
+  TORCH_CHECK(x.size(0) == M, "shape mismatch");
+  if (M == 0 || N == 0 || K == 0)
+    return gemm_strided(g, 1, N, x, K, 1, c10::nullopt, N, K, M);
+  return bns::gemm_tiled(bns::GEMM_TN, g, x, c10::nullopt, N, K, M,
+                         bns::DROP_B, (float)keep, (uint64_t)seed);
 }
 
 }  // namespace
@@ -2040,9 +2061,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("scatter_add_rows", &scatter_add_rows, "scatter-add rows + scale");
   m.def("philox_keys", &philox_keys, "BNS sampling keys (Philox4x32-10)");
   m.def("syncbn_stats", &syncbn_stats, "column sum + sum of squares");
-  m.def("gemm_nt_bias", &gemm_nt_bias, "fp32 MFMA GEMM x@w^T+b");
-  m.def("gemm_nn", &gemm_nn, "fp32 MFMA GEMM g@w");
-  m.def("gemm_tn", &gemm_tn, "fp32 MFMA GEMM g^T@x");
+  // kernel: 0 = routed by shape, 1 = 64x64 kernel, 2 = tiled 128x128 kernel
+  m.def("gemm_nt_bias", &gemm_nt_bias, "fp32 MFMA GEMM x@w^T+b",
+        py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("kernel") = 0);
+  m.def("gemm_nn", &gemm_nn, "fp32 MFMA GEMM g@w", py::arg("g"),
+        py::arg("w"), py::arg("kernel") = 0);
+  m.def("gemm_tn", &gemm_tn, "fp32 MFMA GEMM g^T@x", py::arg("g"),
+        py::arg("x"), py::arg("kernel") = 0);
+  m.def("gemm_nt_bias_drop", &gemm_nt_bias_drop,
+        "tiled GEMM dropout(x)@w^T+b, dropout fused into the operand load");
+  m.def("gemm_tn_drop", &gemm_tn_drop,
+        "tiled GEMM g^T@dropout(x), dropout fused into the operand load");
   m.def("sddmm_add", &sddmm_add, "GAT u_add_v SDDMM");
   m.def("segment_softmax", &segment_softmax, "edge softmax by dst segment");
   m.def("segment_softmax_backward", &segment_softmax_backward,

@@ -16,8 +16,10 @@ setup(
     ext_modules=[
         CUDAExtension(
             "bnsgcn_amd._C",
-            sources=["bnsgcn_amd/ops/hip/kernels.hip"],
-            depends=["bnsgcn_amd/ops/hip/common.h"],
+            sources=["bnsgcn_amd/ops/hip/kernels.hip",
+                     "bnsgcn_amd/ops/hip/gemm_tiled.hip"],
+            depends=["bnsgcn_amd/ops/hip/common.h",
+                     "bnsgcn_amd/ops/hip/gemm_tiled.h"],
             extra_compile_args={"nvcc": ["-O3"], "cxx": ["-O3"]},
         )
     ],
