@@ -58,12 +58,23 @@ class GraphContext:
         self.out_norm_inv = _inv_sqrt(out_deg)     # GCN src scale
         self.in_deg_inv = _inv(in_deg)             # SAGE mean dst scale
         self.n_rows = self.indptr.numel() - 1
+        self.rowgroup_ratio = (None, None)
         if dev.type == "cuda":
             # pre-build SpMM work lists on the default stream (avoids
             # cross-stream allocation of cached plan tensors)
-            from ..ops.functional import _worklist_of
-            _worklist_of(self.indptr)
-            _worklist_of(self.t_indptr)
+            from ..ops import functional as BF
+            BF._worklist_of(self.indptr)
+            BF._worklist_of(self.t_indptr)
+            # the inner CSRs are static for the whole run: row-group form
+            # for the wide SpMM, kept only where it saves row reads
+            # (entries/edges per CSR, None = not built). The transposed
+            # CSR always, the forward one on request (BF.GROUP_FWD).
+            n_src = self.n_rows if plan is None else plan.n_inner
+            self.rowgroup_ratio = (
+                BF.attach_rowgroups(self.indptr, self.indices, n_src)
+                if BF.GROUP_FWD else None,
+                BF.attach_rowgroups(self.t_indptr, self.t_indices,
+                                    self.n_rows))
         # lazily built per-epoch GAT block (combined inner+halo CSR)
         self._gat_cache: tuple[int, tuple] | None = None
         # full-halo (p=1.0) exchange state for precompute / GAT layer 0

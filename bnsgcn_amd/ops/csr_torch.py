@@ -7,6 +7,8 @@ precomputed CSR fragments, cheap enough for the epoch loop.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
 
@@ -112,6 +114,97 @@ def build_worklist(indptr: torch.Tensor, seg: int = None, max_waves: int = None
     wave_start[-1] = total
     return (wrow.contiguous(), wbeg.contiguous(), wend.contiguous(),
             wave_start.contiguous(), zero_rows)
+
+
+# Row-group defaults from the on-device sweep at F = 256 on the Reddit-shaped
+# graph (profiles/BENCH_SUMMARY_rowgroup.md).
+GROUP_R = int(os.environ.get("BNSGCN_SPMM_GROUP_R", 4))   # rows per group
+GSEG = int(os.environ.get("BNSGCN_GSEG", 1024))           # entries per item
+GROUP_W_MAX = 255                                         # uint8 weight field
+
+
+class RowGroups(NamedTuple):
+    """Row-group form of a static CSR (build_rowgroups)."""
+    R: int
+    sched: tuple            # (wgroup, wbeg, wend, wave_start) as build_worklist
+    ecol: torch.Tensor      # int32 [n_entries] source column of each entry
+    ew: torch.Tensor        # uint8 [n_entries, R] edge count per row of group
+    zero_rows: torch.Tensor  # int64 rows the kernel does not fully overwrite
+    ratio: float            # n_entries / n_edges (1.0 for an edgeless CSR)
+
+
+def build_rowgroups(indptr: torch.Tensor, indices: torch.Tensor, n_cols: int,
+                    R: int = None, gseg: int = None, max_waves: int = None
+                    ) -> RowGroups:
+    """Regroup a static CSR so that the wide SpMM reads a source row once
+    per group of R consecutive destination rows (group = row // R, the last
+    one may be partial) instead of once per edge.
+
+    A group's edge list becomes its DISTINCT source columns in ascending
+    order; entry e carries R uint8 weights, ew[e, r] = how many times row
+    group * R + r has the edge (0: it has none). A count above 255 is never
+    clamped: the entry is repeated, each repeat carrying at most 255 of it.
+
+    The schedule is build_worklist's, run over the groups' entry ranges with
+    seg = gseg: an item is (group, <= gseg entries), a group longer than
+    gseg is split and stored bitwise negated (its rows combine with
+    atomicAdd), items keep ascending group order, waves own contiguous item
+    ranges balanced by entry count, n_waves % 8 == 0. Hub rows stay in
+    their groups — gseg is what caps the work of one wave.
+
+    zero_rows = rows of split groups + rows with no edge (the kernel stores
+    a row only if the item holds an entry for it). `ratio` is what the
+    caller's keep rule reads: the kernel's source-row reads per edge.
+    """
+    R = R or GROUP_R
+    gseg = gseg or GSEG
+    device = indptr.device
+    n = indptr.numel() - 1
+    deg = indptr[1:] - indptr[:-1]
+    E = int(indices.numel())
+    n_groups = (n + R - 1) // R
+    row = torch.repeat_interleave(torch.arange(n, device=device), deg)
+    # one sorted pass: key = ((group, col), r); equal keys = parallel edges
+    key = ((row // R) * n_cols + indices.long()) * R + row % R
+    del row
+    ukey, cnt = torch.unique(key, return_counts=True)
+    del key
+    pair, r = ukey // R, ukey % R
+    del ukey
+    # entry id of each (pair, r): distinct (group, col) in ascending order
+    pcol, inv = torch.unique_consecutive(pair, return_inverse=True)
+    egroup, ecol = pcol // n_cols, pcol % n_cols
+    n_pairs = pcol.numel()
+    # repeats of an entry = ceil(largest count among its rows / 255)
+    nrep = (cnt + (GROUP_W_MAX - 1)) // GROUP_W_MAX
+    reps = torch.zeros(n_pairs, dtype=torch.int64, device=device)
+    reps.scatter_reduce_(0, inv, nrep, "amax", include_self=True)
+    first = torch.cumsum(reps, 0) - reps
+    n_ent = int(reps.sum())
+    ew = torch.zeros(n_ent, R, dtype=torch.uint8, device=device)
+    ew[first[inv], r] = cnt.clamp(max=GROUP_W_MAX).to(torch.uint8)
+    over = torch.nonzero(nrep > 1, as_tuple=True)[0]
+    if over.numel():
+        # j-th repeat (j >= 1) carries min(255, count - 255 j)
+        k = nrep[over] - 1
+        src = torch.repeat_interleave(over, k)
+        j = (torch.arange(src.numel(), device=device)
+             - torch.repeat_interleave(torch.cumsum(k, 0) - k, k) + 1)
+        ew[first[inv[src]] + j, r[src]] = (
+            (cnt[src] - GROUP_W_MAX * j).clamp(max=GROUP_W_MAX)
+            .to(torch.uint8))
+    ecol = torch.repeat_interleave(ecol, reps).to(torch.int32)
+    egroup = torch.repeat_interleave(egroup, reps)
+    gptr = torch.searchsorted(
+        egroup, torch.arange(n_groups + 1, device=device)).to(torch.int64)
+    wgroup, wbeg, wend, wave_start, zero_groups = build_worklist(
+        gptr, seg=gseg, max_waves=max_waves)
+    glen = gptr[1:] - gptr[:-1]
+    split = (glen > gseg)[torch.arange(n, device=device) // R]
+    zero_rows = torch.nonzero(split | (deg == 0), as_tuple=True)[0]
+    return RowGroups(R, (wgroup, wbeg, wend, wave_start), ecol.contiguous(),
+                     ew.contiguous(), zero_rows,
+                     n_ent / E if E else 1.0)
 
 
 def merge_csr(ip1: torch.Tensor, ix1: torch.Tensor,

@@ -28,8 +28,60 @@ def _worklist_of(indptr):
     return wl
 
 
+import os as _os
+
+# Row-group SpMM (csr_torch.build_rowgroups + spmm_sum_grouped_kernel) for
+# static CSRs. BNSGCN_SPMM_GROUP=0 turns the path off. The format is kept
+# only when it asks for at most GROUP_TAU source-row reads per edge: above
+# that the grouped kernel no longer beats the per-row one by more than the
+# latter's repeat spread (profiles/BENCH_SUMMARY_rowgroup.md), and a graph
+# without shared neighbours pays neither time nor memory.
+_GROUP = _os.environ.get("BNSGCN_SPMM_GROUP", "1") != "0"
+GROUP_TAU = float(_os.environ.get("BNSGCN_SPMM_GROUP_TAU", 0.6))
+# GraphContext groups the TRANSPOSED inner CSR only (the backward SpMM).
+# transpose_csr leaves its rows in ascending column order, which is the
+# grouped kernel's summation order, and what the backward produces feeds
+# no activation mask, so the step's results move by rounding alone. The
+# forward CSR's rows are in edge order: grouping it re-orders every row's
+# sum, the fused LayerNorm+ReLU after the layer then flips a few dozen of
+# its 60M mask bits, and the gradients of a step move by up to 7e-4 of
+# their largest element (profiles/BENCH_SUMMARY_rowgroup.md) — the size of
+# the per-row path's own run-to-run change when a hub row's atomics land
+# in another order, but on every run. BNSGCN_SPMM_GROUP_FWD=1 groups it too.
+GROUP_FWD = _os.environ.get("BNSGCN_SPMM_GROUP_FWD", "0") == "1"
+
+
+def attach_rowgroups(indptr, indices, n_cols):
+    """Build the row-group form of a STATIC CSR, apply the keep rule and
+    cache the result on the indptr tensor (`_bns_rowgroups`, lifetime of
+    `_bns_worklist`). Returns the builder's entries/edges ratio, or None
+    when the path is off or the CSR is not on the GPU."""
+    if not (_GROUP and indptr.is_cuda):
+        return None
+    from .csr_torch import build_rowgroups
+    rg = build_rowgroups(indptr, indices, n_cols)
+    keep = rg.ratio <= GROUP_TAU
+    if keep:
+        indptr._bns_rowgroups = rg
+    if _os.environ.get("BNSGCN_SPMM_GROUP_LOG") == "1":
+        print(f"rowgroup: R={rg.R} entries/edges {rg.ratio:.3f} "
+              f"({indices.numel()} edges) -> {'kept' if keep else 'dropped'}",
+              flush=True)
+    return rg.ratio
+
+
 def spmm_sum_raw(indptr, indices, x, src_scale=None, dst_scale=None, out=None):
     if use_hip(x):
+        rg = getattr(indptr, "_bns_rowgroups", None) if _GROUP else None
+        if rg is not None and x.shape[1] % 4 == 0 and x.shape[1] // 4 > 32:
+            acc = out is not None
+            if not acc:
+                out = torch.empty(indptr.numel() - 1, x.shape[1],
+                                  dtype=x.dtype, device=x.device)
+                if rg.zero_rows.numel():
+                    out.index_fill_(0, rg.zero_rows, 0.0)
+            return get_ext().spmm_sum_grouped(*rg.sched, rg.ecol, rg.ew, x,
+                                              src_scale, dst_scale, out, acc)
         wrow, wbeg, wend, wave_start, zero_rows = _worklist_of(indptr)
         acc = out is not None
         if not acc:
@@ -277,8 +329,6 @@ class _SegmentSoftmax(Function):
 def segment_softmax(logits, indptr):
     return _SegmentSoftmax.apply(logits, indptr)
 
-
-import os as _os
 
 # GEMM dispatch (K6). Two hand-written fp32 MFMA kernels live behind
 # gemm_nt_bias / gemm_nn / gemm_tn: the 64x64 gemm_f32_kernel and the tiled

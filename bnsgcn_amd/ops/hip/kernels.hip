@@ -79,6 +79,147 @@ __global__ __launch_bounds__(256) void spmm_sum_vec4_kernel(
   }
 }
 
+// Row-group form for a STATIC CSR and wide rows (f4 > 32): the schedule's
+// "row" is a group of R consecutive destination rows and an item is a
+// range of that group's entries — its distinct source columns, ascending,
+// each with R uint8 edge counts (ops/csr_torch.build_rowgroups). The wave
+// reads an entry's source row ONCE and adds it to every row of the group
+// that has the edge: rows = consecutive ids of a locality-ordered
+// partition share neighbours, so this asks for a fraction of the 1-KiB
+// row reads the per-row kernel issues (entries / edges, the builder's
+// `ratio`). Lane l owns float4 l (and l + 64 when NV = 2) of all R rows:
+// R * NV float4 accumulators.
+// Column id, src scale and the weight words of 64 entries arrive with one
+// coalesced load each and are broadcast with readlane, so everything that
+// steers an entry is wave-uniform: the test `w != 0` is a scalar branch.
+// It is a correctness requirement, not an optimisation — a branch-free
+// 0 * v would carry an inf/NaN of the source row into rows that have no
+// edge to it. Four row reads are issued before the first accumulate.
+// Within a row, terms are added in ascending column order, so a row of an
+// unsplit group is bit-reproducible from run to run.
+template <int NW>
+DEV_INLINE void load_group_w(const uint32_t* __restrict__ p, uint32_t (&w)[NW]) {
+  if constexpr (NW == 1) {
+    w[0] = *p;
+  } else {
+    static_assert(NW == 2, "R in {4, 8}");
+    const uint2 t = *reinterpret_cast<const uint2*>(p);
+    w[0] = t.x; w[1] = t.y;
+  }
+}
+
+template <bool ACC, int R, int NV>
+__global__ __launch_bounds__(256) void spmm_sum_grouped_kernel(
+    const int32_t* __restrict__ wgroup, const int64_t* __restrict__ wbeg,
+    const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
+    const int32_t* __restrict__ ecol, const uint32_t* __restrict__ ew,
+    const float* __restrict__ x, const float* __restrict__ src_scale,
+    const float* __restrict__ dst_scale, float* __restrict__ out, int f4,
+    int n_rows) {
+  constexpr int NW = R / 4;                  // 32-bit weight words per entry
+  constexpr int U = 4;                       // row reads in flight
+  const WorkList wl = {wgroup, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<WAVE>(wl);
+  const int lane = wi.lane;
+  const int it_beg = __builtin_amdgcn_readfirstlane(wi.beg);
+  const int it_end = __builtin_amdgcn_readfirstlane(wi.end);
+  const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
+  float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
+  const float4 zero4 = {0.f, 0.f, 0.f, 0.f};
+
+  for (int it = it_beg; it < it_end; ++it) {
+    const WorkItem wk = work_item(wl, it);   // wk.row = group id
+    for (int f0 = 0; f0 < f4; f0 += NV * WAVE) {
+      // a lane past the row's end reads the row's last float4 instead
+      // (in bounds, one unconditional 16-byte load) and never stores
+      int fi[NV];
+      bool has[NV];
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        fi[v] = f0 + v * WAVE + lane;
+        has[v] = fi[v] < f4;
+        if (!has[v]) fi[v] = f4 - 1;
+      }
+      float4 acc[NV][R];
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[v][r] = zero4;
+      uint32_t seen[NW];                     // OR of the item's weight words
+#pragma unroll
+      for (int j = 0; j < NW; ++j) seen[j] = 0u;
+
+      // one entry: add row `val` to every row of the group with w != 0
+      auto accumulate = [&](int k, const float4 (&val)[NV], int ssc,
+                            const uint32_t (&wv)[NW]) {
+        const float ss = __int_as_float(__builtin_amdgcn_readlane(ssc, k));
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+          const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)wv[j], k);
+          seen[j] |= w;
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            const uint32_t cnt = (w >> (8 * b)) & 0xffu;
+            if (cnt != 0u) {
+              const float s = (float)cnt * ss;
+#pragma unroll
+              for (int v = 0; v < NV; ++v) f4_axpy(acc[v][4 * j + b], s, val[v]);
+            }
+          }
+        }
+      };
+
+      for (int64_t e0 = wk.beg; e0 < wk.end; e0 += WAVE) {
+        const int nv = (int)((wk.end - e0 < WAVE) ? (wk.end - e0) : WAVE);
+        int cid = 0, ssc = __float_as_int(1.0f);
+        uint32_t wv[NW];
+#pragma unroll
+        for (int j = 0; j < NW; ++j) wv[j] = 0u;
+        if (lane < nv) {
+          cid = ecol[e0 + lane];
+          if (src_scale) ssc = __float_as_int(src_scale[cid]);
+          load_group_w<NW>(ew + (e0 + lane) * NW, wv);
+        }
+        int k = 0;
+        for (; k + U <= nv; k += U) {
+          float4 val[U][NV];
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            const int64_t base =
+                (int64_t)__builtin_amdgcn_readlane(cid, k + u) * f4;
+#pragma unroll
+            for (int v = 0; v < NV; ++v)
+              val[u][v] = x4[base + fi[v]];
+          }
+#pragma unroll
+          for (int u = 0; u < U; ++u) accumulate(k + u, val[u], ssc, wv);
+        }
+        for (; k < nv; ++k) {
+          float4 val[NV];
+          const int64_t base = (int64_t)__builtin_amdgcn_readlane(cid, k) * f4;
+#pragma unroll
+          for (int v = 0; v < NV; ++v) val[v] = x4[base + fi[v]];
+          accumulate(k, val, ssc, wv);
+        }
+      }
+
+      // a row is stored only if the item holds an entry for it
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int row = wk.row * R + r;
+        if (((seen[r / 4] >> (8 * (r % 4))) & 0xffu) != 0u && row < n_rows) {
+          const float ds = dst_scale ? dst_scale[row] : 1.0f;
+          const int64_t ob = (int64_t)row * f4;
+#pragma unroll
+          for (int v = 0; v < NV; ++v)
+            if (has[v])
+              store_row<ACC>(&out4[ob + fi[v]], acc[v][r], wk.atomic, ds);
+        }
+      }
+    }
+  }
+}
+
 // Narrow rows (f4 <= G float4, e.g. the 41->44-wide projected output
 // layer): a row is at most G lanes wide, so the half-wave form above
 // leaves most lanes without a load. Here the wave is EDGE-parallel
@@ -1527,6 +1668,68 @@ at::Tensor spmm_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
   return out;
 }
 
+// Row-group SpMM (spmm_sum_grouped_kernel): same contract as spmm_sum on
+// the format of ops/csr_torch.build_rowgroups — (wgroup, wbeg, wend,
+// wave_start) schedule the entries (ecol, ew[n_entries, R]); `out` is
+// caller-allocated with the builder's zero_rows pre-zeroed unless acc.
+template <int R>
+void launch_grouped(const WorkListArgs& wl, bool acc, int f4,
+                    const at::Tensor& ecol, const at::Tensor& ew,
+                    const at::Tensor& x, const float* ss, const float* ds,
+                    at::Tensor& out) {
+  auto launch = [&](auto kernel) {
+    launch_worklist(kernel, wl, 64, ecol.data_ptr<int32_t>(),
+                    reinterpret_cast<const uint32_t*>(ew.data_ptr<uint8_t>()),
+                    x.data_ptr<float>(), ss, ds, out.data_ptr<float>(), f4,
+                    (int)out.size(0));
+  };
+  if (f4 > 64)                      // a second float4 per lane
+    launch(acc ? spmm_sum_grouped_kernel<true, R, 2>
+               : spmm_sum_grouped_kernel<false, R, 2>);
+  else
+    launch(acc ? spmm_sum_grouped_kernel<true, R, 1>
+               : spmm_sum_grouped_kernel<false, R, 1>);
+}
+
+at::Tensor spmm_sum_grouped(at::Tensor wgroup, at::Tensor wbeg,
+                            at::Tensor wend, at::Tensor wave_start,
+                            at::Tensor ecol, at::Tensor ew, at::Tensor x,
+                            c10::optional<at::Tensor> src_scale,
+                            c10::optional<at::Tensor> dst_scale,
+                            at::Tensor out, bool acc) {
+  check_f32(x, "x");
+  check_f32(out, "out");
+  const WorkListArgs wl = worklist_args(wgroup, wbeg, wend, wave_start);
+  TORCH_CHECK(ecol.scalar_type() == at::kInt && ecol.is_cuda() &&
+                  ecol.is_contiguous(), "ecol: contiguous int32 expected");
+  TORCH_CHECK(ew.scalar_type() == at::kByte && ew.is_cuda() &&
+                  ew.is_contiguous() && ew.dim() == 2 &&
+                  ew.size(0) == ecol.numel(),
+              "ew: contiguous uint8 [n_entries, R] expected");
+  const int R = (int)ew.size(1);
+  const int F = x.size(1);
+  TORCH_CHECK(F % 4 == 0 && F / 4 > 32,
+              "spmm_sum_grouped covers F % 4 == 0 with F / 4 > 32, got F = ",
+              F);
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == F, "out: [n_rows, F] expected");
+  if (src_scale.has_value())
+    TORCH_CHECK(src_scale->numel() == x.size(0), "src_scale: one per x row");
+  if (dst_scale.has_value())
+    TORCH_CHECK(dst_scale->numel() == out.size(0),
+                "dst_scale: one per out row");
+  if (wgroup.numel() == 0 || wl.n_waves <= 0) return out;
+  const float* ss = opt_ptr(src_scale);
+  const float* ds = opt_ptr(dst_scale);
+  switch (R) {
+    case 4: launch_grouped<4>(wl, acc, F / 4, ecol, ew, x, ss, ds, out); break;
+    case 8: launch_grouped<8>(wl, acc, F / 4, ecol, ew, x, ss, ds, out); break;
+    // R = 16 was built and measured: slower than the per-row kernel at
+    // every gseg (profiles/BENCH_SUMMARY_rowgroup.md), so not instantiated
+    default: TORCH_CHECK(false, "spmm_sum_grouped: R must be 4 or 8, got ", R);
+  }
+  return out;
+}
+
 at::Tensor pack_rows(at::Tensor x, at::Tensor idx,
                      c10::optional<at::Tensor> scale) {
   check_f32(x, "x");
@@ -2057,6 +2260,8 @@ at::Tensor gemm_tn_drop(at::Tensor g, at::Tensor x, double keep,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("spmm_sum", &spmm_sum, "CSR SpMM sum with fused src/dst scales");
+  m.def("spmm_sum_grouped", &spmm_sum_grouped,
+        "row-group CSR SpMM sum with fused src/dst scales");
   m.def("pack_rows", &pack_rows, "gather rows + per-row scale");
   m.def("scatter_add_rows", &scatter_add_rows, "scatter-add rows + scale");
   m.def("philox_keys", &philox_keys, "BNS sampling keys (Philox4x32-10)");

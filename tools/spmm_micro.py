@@ -12,6 +12,16 @@ the transposed CSR (what the backward runs) — over all destination rows
 and/or over the 66 % train rows only, as the final layer does. That is
 the kernel-only before/after for the narrow-F path (F <= 64 takes
 spmm_sum_narrow_kernel unless BNSGCN_SPMM_NARROW_MAX=0).
+
+  python tools/spmm_micro.py --graph reddit --grouped \
+      --group-r 4,8,16 --gseg 512,1024,4096 [--permute]
+
+--grouped compares, per CSR (forward and transposed) and width, the per-row
+kernel (median and max - min spread of --repeats timings) with the
+row-group kernel for every (R, gseg): entries/edges, build time, format
+size and kernel time. --permute relabels the nodes with a random
+permutation first, which removes the id locality (the graph for finding
+the keep threshold GROUP_TAU).
 """
 import argparse
 import os
@@ -27,16 +37,24 @@ from bnsgcn_amd.graph import CSR
 from bnsgcn_amd.ops.functional import spmm_sum_raw
 
 
-def toy_csr():
+def _relabel(src, dst, n, permute):
+    if not permute:
+        return src, dst
+    p = np.random.default_rng(1).permutation(n)
+    return p[src], p[dst]
+
+
+def toy_csr(permute=False):
     rng = np.random.default_rng(0)
     n, e = 200_000, 20_000_000
     # power-law-ish columns with locality
     src = (rng.random(e) ** 4 * n).astype(np.int64)
     dst = np.sort(rng.integers(0, n, e))
+    src, dst = _relabel(src, dst, n, permute)
     return CSR.from_edges(src, dst, n, n), None
 
 
-def reddit_csr():
+def reddit_csr(permute=False):
     """(in-edge CSR, train-row ids) of the Reddit-shaped synthetic graph."""
     from bnsgcn_amd.graph.csr import add_self_loops
     from bnsgcn_amd.graph.synthetic import DATASETS, _draw_edges
@@ -44,6 +62,7 @@ def reddit_csr():
     rng = np.random.default_rng(0)
     src, dst = _draw_edges(spec, spec.n_nodes, spec.n_edges, rng)
     src, dst = add_self_loops(src, dst, spec.n_nodes)
+    src, dst = _relabel(src, dst, spec.n_nodes, permute)
     c = CSR.from_edges(src, dst, spec.n_nodes, spec.n_nodes)
     train = np.nonzero(rng.random(spec.n_nodes) < spec.train_frac)[0]
     return c, train
@@ -74,6 +93,43 @@ def device_csrs(c, train, which):
                                           ip.numel() - 1)]
 
 
+def grouped_table(label, ip, ix, n_src, F, a):
+    """Per-row kernel against the row-group kernel on one CSR."""
+    from bnsgcn_amd.ops.csr_torch import build_rowgroups
+    e = ix.numel()
+    x = torch.randn(n_src, F, device="cuda")
+    base = [time_call(lambda: spmm_sum_raw(ip, ix, x), a.iters)
+            for _ in range(a.repeats)]
+    med, spread = float(np.median(base)), max(base) - min(base)
+    print(f"{label} F={F} {e} edges: per-row {med*1e3:.3f} ms "
+          f"(spread {spread*1e3:.3f} over {a.repeats} x {a.iters})",
+          flush=True)
+    for R in (int(r) for r in a.group_r.split(",")):
+        for gseg in (int(g) for g in a.gseg.split(",")):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rg = build_rowgroups(ip, ix, n_src, R=R, gseg=gseg)
+            torch.cuda.synchronize()
+            t_build = time.perf_counter() - t0
+            ipg = ip.clone()
+            ipg._bns_rowgroups = rg
+            ts = [time_call(lambda: spmm_sum_raw(ipg, ix, x), a.iters)
+                  for _ in range(a.repeats)]
+            ref = spmm_sum_raw(ip, ix, x)
+            got = spmm_sum_raw(ipg, ix, x)
+            err = float((got - ref).abs().max() / ref.abs().max())
+            mb = (rg.ecol.numel() * (4 + R)
+                  + sum(t.numel() * t.element_size() for t in rg.sched)) / 1e6
+            print(f"  R={R} gseg={gseg}: entries/edges {rg.ratio:.3f}, "
+                  f"{rg.sched[0].numel()} items, "
+                  f"{int((rg.sched[0] < 0).sum())} of split groups, "
+                  f"build {t_build*1e3:.0f} ms, {mb:.0f} MB, grouped "
+                  f"{np.median(ts)*1e3:.3f} ms (spread "
+                  f"{(max(ts)-min(ts))*1e3:.3f}), x{med/np.median(ts):.2f}, "
+                  f"max|diff|/max|ref| {err:.1e}", flush=True)
+            del rg, ipg, ref, got
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--graph", choices=["toy", "reddit"], default="toy")
@@ -82,17 +138,27 @@ def main():
     p.add_argument("--rows", default="full",
                    help="comma-separated subset of full,train")
     p.add_argument("--iters", type=int, default=5)
+    p.add_argument("--grouped", action="store_true",
+                   help="per-row against row-group kernel (module docstring)")
+    p.add_argument("--group-r", default="4,8,16")
+    p.add_argument("--gseg", default="512,1024,4096")
+    p.add_argument("--repeats", type=int, default=3)
+    p.add_argument("--permute", action="store_true",
+                   help="relabel nodes randomly (no id locality)")
     a = p.parse_args()
     assert torch.cuda.is_available()
-    c, train = toy_csr() if a.graph == "toy" else reddit_csr()
+    c, train = (toy_csr if a.graph == "toy" else reddit_csr)(a.permute)
     for which in a.rows.split(","):
         assert which == "full" or train is not None, "toy graph has no rows"
         csrs = device_csrs(c, train, which)
-        if a.graph == "toy":
+        if a.graph == "toy" and not a.grouped:
             csrs = csrs[:1]
         for label, ip, ix, n_src in csrs:
             e = ix.numel()
             for F in (int(f) for f in a.feats.split(",")):
+                if a.grouped:
+                    grouped_table(label, ip, ix, n_src, F, a)
+                    continue
                 x = torch.randn(n_src, F, device="cuda")
                 dt = time_call(lambda: spmm_sum_raw(ip, ix, x), a.iters)
                 gb = e * F * 4 / 1e9
