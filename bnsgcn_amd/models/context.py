@@ -52,6 +52,10 @@ class GraphContext:
         self.loss_rows: torch.Tensor | None = None
         self._rows_static: tuple | None = None   # gathered inner CSRs
         self._rows_halo: tuple | None = None     # per-epoch gathered halo
+        # --agg-dtype (set by the runtime): torch.bfloat16 rounds the source
+        # operand of every aggregate() once to bf16, forward and backward;
+        # None (fp32) leaves it alone. Same rule in train and eval.
+        self.agg_dtype: torch.dtype | None = None
         in_deg = in_deg.to(dev).float()
         out_deg = out_deg.to(dev).float()
         self.in_norm_inv = _inv_sqrt(in_deg)       # GCN dst scale
@@ -124,12 +128,13 @@ class GraphContext:
             from ..ops.functional import spmm_sum
             if rows is None:
                 return spmm_sum(x, *self.inner_csrs, src_scale=src,
-                                dst_scale=dst)
+                                dst_scale=dst, src_dtype=self.agg_dtype)
             ip, ix, tip, tix = self._rows_inner_csrs(rows)
-            return spmm_sum(x, ip, ix, tip, tix, src_scale=src, dst_scale=dst)
+            return spmm_sum(x, ip, ix, tip, tix, src_scale=src, dst_scale=dst,
+                            src_dtype=self.agg_dtype)
         if rows is None:
             return partition_aggregate(x, self.plan, self.inner_csrs, src,
-                                       dst, halo_src)
+                                       dst, halo_src, self.agg_dtype)
         import dataclasses
         st = self.plan.state
         hfip, hfix, hbip, hbix = self._rows_halo_csrs(rows, st)
@@ -138,9 +143,11 @@ class GraphContext:
                                    halo_bwd_indptr=hbip,
                                    halo_bwd_indices=hbix)
         ip, ix, tip, tix = self._rows_inner_csrs(rows)
+        from ..ops.functional import check_src_dtype
         from ..parallel.halo import _PartitionAggregate
         return _PartitionAggregate.apply(x, self.plan, st_r, ip, ix, tip, tix,
-                                         src, dst, halo_src)
+                                         src, dst, halo_src,
+                                         check_src_dtype(self.agg_dtype))
 
     def _rows_inner_csrs(self, rows: torch.Tensor):
         """Row-gathered inner CSR + transpose, cached (rows are static)."""

@@ -70,14 +70,31 @@ def attach_rowgroups(indptr, indices, n_cols):
     return rg.ratio
 
 
+def round_bf16_raw(x):
+    """The source operand of --agg-dtype bf16: x rounded once to bf16,
+    round to nearest even. On the GPU the HIP cast kernel returns a bf16
+    tensor, which spmm_sum_raw / pack_rows_raw read at half the bytes. On
+    the CPU the rounded values float(bf16(float32(x))) are carried in x's
+    own dtype, so a float64 run is a float64 oracle of the same numbers."""
+    if use_hip(x) and x.dtype == torch.float32:
+        return get_ext().cast_bf16(x.contiguous())
+    return x.float().bfloat16().to(x.dtype)
+
+
 def spmm_sum_raw(indptr, indices, x, src_scale=None, dst_scale=None, out=None):
+    """x may be a bf16 source (round_bf16_raw); the result is fp32 then.
+    The bf16 kernels cover F % 4 == 0: other widths upcast the rounded
+    copy and take the fp32 kernels — the same numbers, no byte saving."""
+    if x.dtype == torch.bfloat16 and not (use_hip(x) and x.shape[1] % 4 == 0):
+        x = x.float()
     if use_hip(x):
+        odt = torch.float32 if x.dtype == torch.bfloat16 else x.dtype
         rg = getattr(indptr, "_bns_rowgroups", None) if _GROUP else None
         if rg is not None and x.shape[1] % 4 == 0 and x.shape[1] // 4 > 32:
             acc = out is not None
             if not acc:
                 out = torch.empty(indptr.numel() - 1, x.shape[1],
-                                  dtype=x.dtype, device=x.device)
+                                  dtype=odt, device=x.device)
                 if rg.zero_rows.numel():
                     out.index_fill_(0, rg.zero_rows, 0.0)
             return get_ext().spmm_sum_grouped(*rg.sched, rg.ecol, rg.ew, x,
@@ -88,7 +105,7 @@ def spmm_sum_raw(indptr, indices, x, src_scale=None, dst_scale=None, out=None):
             # allocate uninitialized and zero ONLY the rows the kernel does
             # not fully overwrite (split/atomic + empty rows)
             out = torch.empty(indptr.numel() - 1, x.shape[1],
-                              dtype=x.dtype, device=x.device)
+                              dtype=odt, device=x.device)
             if zero_rows.numel():
                 out.index_fill_(0, zero_rows, 0.0)
         return get_ext().spmm_sum(wrow, wbeg, wend, wave_start, indices, x,
@@ -149,8 +166,11 @@ def segment_softmax_bwd_raw(indptr, alpha, grad_alpha):
 
 
 def pack_rows_raw(x, idx, scale=None):
+    """A bf16 x (round_bf16_raw) packs to fp32 rows float(x[idx]) * scale."""
     if use_hip(x):
         return get_ext().pack_rows(x, idx, scale)
+    if x.dtype == torch.bfloat16:
+        x = x.float()
     return ref.pack_rows(x, idx, scale)
 
 
@@ -168,25 +188,44 @@ class _SpMMSum(Function):
 
     Backward runs the SAME kernel on the precomputed transposed CSR with the
     scale roles swapped — no atomics anywhere (SURVEY.md §7 'per-epoch block
-    assembly' design)."""
+    assembly' design).
+
+    src_dtype=torch.bfloat16 (--agg-dtype bf16) rounds the source operand
+    once to bf16 in both directions — x in forward, grad in backward
+    (straight-through: the rounding has derivative 1). Scales, products,
+    accumulation and the result stay fp32."""
 
     @staticmethod
-    def forward(ctx, x, indptr, indices, indptr_t, indices_t, src_scale, dst_scale):
+    def forward(ctx, x, indptr, indices, indptr_t, indices_t, src_scale,
+                dst_scale, src_dtype=None):
         ctx.save_for_backward(indptr_t, indices_t, src_scale, dst_scale)
+        ctx.src_dtype = src_dtype
+        if src_dtype == torch.bfloat16:
+            x = round_bf16_raw(x)
         return spmm_sum_raw(indptr, indices, x, src_scale, dst_scale)
 
     @staticmethod
     def backward(ctx, grad):
         indptr_t, indices_t, src_scale, dst_scale = ctx.saved_tensors
-        gx = spmm_sum_raw(indptr_t, indices_t, grad.contiguous(),
+        grad = grad.contiguous()
+        if ctx.src_dtype == torch.bfloat16:
+            grad = round_bf16_raw(grad)
+        gx = spmm_sum_raw(indptr_t, indices_t, grad,
                           src_scale=dst_scale, dst_scale=src_scale)
-        return gx, None, None, None, None, None, None
+        return gx, None, None, None, None, None, None, None
+
+
+def check_src_dtype(src_dtype):
+    if src_dtype not in (None, torch.float32, torch.bfloat16):
+        raise ValueError(f"aggregation source dtype must be None, "
+                         f"torch.float32 or torch.bfloat16, got {src_dtype}")
+    return torch.bfloat16 if src_dtype == torch.bfloat16 else None
 
 
 def spmm_sum(x, indptr, indices, indptr_t, indices_t,
-             src_scale=None, dst_scale=None):
+             src_scale=None, dst_scale=None, src_dtype=None):
     return _SpMMSum.apply(x, indptr, indices, indptr_t, indices_t,
-                          src_scale, dst_scale)
+                          src_scale, dst_scale, check_src_dtype(src_dtype))
 
 
 class _SpMMEdge(Function):

@@ -70,6 +70,45 @@ DEV_INLINE Chunk load_chunk(const int32_t* __restrict__ indices,
   return c;
 }
 
+// ------------------------------------------------------------ source rows
+// Element type of a gathered source matrix: float, or bf16 carried as its
+// 16 raw bits (--agg-dtype bf16: the source operand was rounded once by
+// cast_bf16_kernel, everything after the load is fp32). load_src4(x, i)
+// returns elements 4i .. 4i+3 as fp32: one 16-byte load for float, one
+// 8-byte load for bf16. bf16 -> fp32 is exact (the 16 bits are the high
+// half of the fp32 word), so the expansion is a shift or a mask and a
+// kernel templated on the source type differs in the load alone.
+typedef uint16_t bf16_t;
+
+DEV_INLINE float4 load_src4(const float* __restrict__ x, int64_t i) {
+  return reinterpret_cast<const float4*>(x)[i];
+}
+DEV_INLINE float4 load_src4(const bf16_t* __restrict__ x, int64_t i) {
+  const uint2 p = reinterpret_cast<const uint2*>(x)[i];
+  return make_float4(__uint_as_float(p.x << 16),
+                     __uint_as_float(p.x & 0xffff0000u),
+                     __uint_as_float(p.y << 16),
+                     __uint_as_float(p.y & 0xffff0000u));
+}
+DEV_INLINE float load_src1(const float* __restrict__ x, int64_t i) {
+  return x[i];
+}
+DEV_INLINE float load_src1(const bf16_t* __restrict__ x, int64_t i) {
+  return __uint_as_float((uint32_t)x[i] << 16);
+}
+
+// fp32 -> bf16 bits, round to nearest even, in integer arithmetic so that
+// denormals round like every other value whatever the FP mode: add 0x7fff
+// plus the lowest kept bit, keep the high half. The carry does the rest —
+// a tie goes to the even neighbour, the largest finite fp32 becomes inf,
+// +-inf and +-0 pass through. NaN (which the add could turn into inf) is
+// the quiet NaN 0x7fc0, as torch's scalar conversion gives.
+DEV_INLINE uint32_t bf16_rne_bits(float f) {
+  const uint32_t u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
 // ------------------------------------------------------------- row store
 DEV_INLINE void atomic_add(float* p, float v) { atomicAdd(p, v); }
 DEV_INLINE void atomic_add(float2* p, float2 v) {

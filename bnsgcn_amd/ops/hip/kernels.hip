@@ -10,6 +10,7 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <c10/util/Optional.h>
 #include <algorithm>
+#include <type_traits>
 #include "common.h"
 #include "gemm_tiled.h"
 
@@ -33,11 +34,13 @@ DEV_INLINE void f4_axpy(float4& a, float ss, const float4 v) {
   a.x += ss * v.x; a.y += ss * v.y; a.z += ss * v.z; a.w += ss * v.w;
 }
 
-template <bool ACC, int SUBW>
+// T = source element type (float, or bf16_t for --agg-dtype bf16): the
+// row read goes through load_src4 (common.h), nothing else depends on it.
+template <typename T, bool ACC, int SUBW>
 __global__ __launch_bounds__(256) void spmm_sum_vec4_kernel(
     const int32_t* __restrict__ wrow, const int64_t* __restrict__ wbeg,
     const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
-    const int32_t* __restrict__ indices, const float* __restrict__ x,
+    const int32_t* __restrict__ indices, const T* __restrict__ x,
     const float* __restrict__ src_scale, const float* __restrict__ dst_scale,
     float* __restrict__ out, int f4) {
   // SUBW = scheduling width: 64 (full wave) for wide rows, 32 (half-wave
@@ -50,7 +53,6 @@ __global__ __launch_bounds__(256) void spmm_sum_vec4_kernel(
   const WorkList wl = {wrow, wbeg, wend, wave_start};
   const WaveItems wi = wave_items<SUBW>(wl);
   const int lane = wi.lane;
-  const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
   float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
 
   for (int it = wi.beg; it < wi.end; ++it) {
@@ -68,8 +70,8 @@ __global__ __launch_bounds__(256) void spmm_sum_vec4_kernel(
           const int c = __shfl(ch.cid, k, SUBW);
           const float ss = src_scale ? __shfl(ch.ssc, k, SUBW) : 1.0f;
           const int64_t base = (int64_t)c * f4;
-          if (hasA) f4_axpy(acc0, ss, x4[base + fA]);
-          if (hasB) f4_axpy(acc1, ss, x4[base + fB]);
+          if (hasA) f4_axpy(acc0, ss, load_src4(x, base + fA));
+          if (hasB) f4_axpy(acc1, ss, load_src4(x, base + fB));
         }
       }
       const int64_t ob = (int64_t)wk.row * f4;
@@ -108,12 +110,12 @@ DEV_INLINE void load_group_w(const uint32_t* __restrict__ p, uint32_t (&w)[NW]) 
   }
 }
 
-template <bool ACC, int R, int NV>
+template <typename T, bool ACC, int R, int NV>
 __global__ __launch_bounds__(256) void spmm_sum_grouped_kernel(
     const int32_t* __restrict__ wgroup, const int64_t* __restrict__ wbeg,
     const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
     const int32_t* __restrict__ ecol, const uint32_t* __restrict__ ew,
-    const float* __restrict__ x, const float* __restrict__ src_scale,
+    const T* __restrict__ x, const float* __restrict__ src_scale,
     const float* __restrict__ dst_scale, float* __restrict__ out, int f4,
     int n_rows) {
   constexpr int NW = R / 4;                  // 32-bit weight words per entry
@@ -123,7 +125,6 @@ __global__ __launch_bounds__(256) void spmm_sum_grouped_kernel(
   const int lane = wi.lane;
   const int it_beg = __builtin_amdgcn_readfirstlane(wi.beg);
   const int it_end = __builtin_amdgcn_readfirstlane(wi.end);
-  const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
   float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
   const float4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
@@ -131,7 +132,8 @@ __global__ __launch_bounds__(256) void spmm_sum_grouped_kernel(
     const WorkItem wk = work_item(wl, it);   // wk.row = group id
     for (int f0 = 0; f0 < f4; f0 += NV * WAVE) {
       // a lane past the row's end reads the row's last float4 instead
-      // (in bounds, one unconditional 16-byte load) and never stores
+      // (in bounds, one unconditional 16-byte load — 8-byte for a bf16
+      // source) and never stores
       int fi[NV];
       bool has[NV];
 #pragma unroll
@@ -189,7 +191,7 @@ __global__ __launch_bounds__(256) void spmm_sum_grouped_kernel(
                 (int64_t)__builtin_amdgcn_readlane(cid, k + u) * f4;
 #pragma unroll
             for (int v = 0; v < NV; ++v)
-              val[u][v] = x4[base + fi[v]];
+              val[u][v] = load_src4(x, base + fi[v]);
           }
 #pragma unroll
           for (int u = 0; u < U; ++u) accumulate(k + u, val[u], ssc, wv);
@@ -198,7 +200,7 @@ __global__ __launch_bounds__(256) void spmm_sum_grouped_kernel(
           float4 val[NV];
           const int64_t base = (int64_t)__builtin_amdgcn_readlane(cid, k) * f4;
 #pragma unroll
-          for (int v = 0; v < NV; ++v) val[v] = x4[base + fi[v]];
+          for (int v = 0; v < NV; ++v) val[v] = load_src4(x, base + fi[v]);
           accumulate(k, val, ssc, wv);
         }
       }
@@ -230,11 +232,11 @@ __global__ __launch_bounds__(256) void spmm_sum_grouped_kernel(
 // partial sums are combined at the end of the item with __shfl_xor over
 // offsets G, 2G, ... (a fixed order, so non-atomic rows stay run-to-run
 // deterministic) and group 0 writes.
-template <bool ACC, int G>
+template <typename T, bool ACC, int G>
 __global__ __launch_bounds__(256) void spmm_sum_narrow_kernel(
     const int32_t* __restrict__ wrow, const int64_t* __restrict__ wbeg,
     const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
-    const int32_t* __restrict__ indices, const float* __restrict__ x,
+    const int32_t* __restrict__ indices, const T* __restrict__ x,
     const float* __restrict__ src_scale, const float* __restrict__ dst_scale,
     float* __restrict__ out, int f4) {
   constexpr int NG = WAVE / G;  // edges per step
@@ -243,7 +245,6 @@ __global__ __launch_bounds__(256) void spmm_sum_narrow_kernel(
   const int lane = wi.lane;
   const int g = lane / G, j = lane % G;
   const bool has = j < f4;
-  const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
   float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
 
   for (int it = wi.beg; it < wi.end; ++it) {
@@ -257,7 +258,8 @@ __global__ __launch_bounds__(256) void spmm_sum_narrow_kernel(
         const int kk = k + g;  // k <= WAVE - NG, so kk < WAVE
         const int c = __shfl(ch.cid, kk, WAVE);
         const float ss = src_scale ? __shfl(ch.ssc, kk, WAVE) : 1.0f;
-        if (has && kk < ch.nv) f4_axpy(acc, ss, x4[(int64_t)c * f4 + j]);
+        if (has && kk < ch.nv)
+          f4_axpy(acc, ss, load_src4(x, (int64_t)c * f4 + j));
       }
     }
 #pragma unroll
@@ -369,7 +371,10 @@ __global__ __launch_bounds__(256) void spmm_sum_scalar_kernel(
 // Scatter destinations can repeat ACROSS peers (a node bordering several
 // partitions) -> atomicAdd (fp32, device scope).
 
-__global__ void pack_rows_kernel(const float* __restrict__ x,
+// T = float or bf16_t (the rounded copy of --agg-dtype bf16): the output is
+// fp32 float(x[idx]) * scale, one fp32 multiply, either way.
+template <typename T>
+__global__ void pack_rows_kernel(const T* __restrict__ x,
                                  const int64_t* __restrict__ idx,
                                  const float* __restrict__ scale,
                                  float* __restrict__ out, int n, int F) {
@@ -379,23 +384,23 @@ __global__ void pack_rows_kernel(const float* __restrict__ x,
   for (int64_t i = t; i < total; i += stride) {
     const int r = i / F, f = i - (int64_t)r * F;
     const float s = scale ? scale[r] : 1.0f;
-    out[i] = s * x[idx[r] * F + f];
+    out[i] = s * load_src1(x, idx[r] * F + f);
   }
 }
 
-__global__ void pack_rows_vec4_kernel(const float* __restrict__ x,
+template <typename T>
+__global__ void pack_rows_vec4_kernel(const T* __restrict__ x,
                                       const int64_t* __restrict__ idx,
                                       const float* __restrict__ scale,
                                       float* __restrict__ out, int n, int f4) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t total = (int64_t)n * f4;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
   float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
   for (int64_t i = t; i < total; i += stride) {
     const int r = i / f4, f = i - (int64_t)r * f4;
     const float s = scale ? scale[r] : 1.0f;
-    const float4 v = x4[idx[r] * f4 + f];
+    const float4 v = load_src4(x, idx[r] * f4 + f);
     out4[i] = make_float4(s * v.x, s * v.y, s * v.z, s * v.w);
   }
 }
@@ -427,6 +432,29 @@ __global__ void scatter_add_rows_kernel(float* __restrict__ out,
       atomicAdd(&out[idx[r] * F + f], s * src[i]);
     }
   }
+}
+
+// ============================== bf16 cast ==============================
+// out = bf16_rne(x) over a flat contiguous array (--agg-dtype bf16 rounds
+// the SpMM's source operand once; bit-identical to torch's CPU
+// .to(torch.bfloat16), NaN payloads aside). Thread i converts elements
+// 4i .. 4i+3 for i < n4 with one 16-byte load and one 8-byte store; the
+// elements from 4 * n4 on go one per thread. n4 = n / 4, or 0 for an x
+// whose base is not 16-byte aligned (a view at an odd offset).
+__global__ __launch_bounds__(256) void cast_bf16_kernel(
+    const float* __restrict__ x, bf16_t* __restrict__ out, int64_t n,
+    int64_t n4) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
+  uint2* __restrict__ out2 = reinterpret_cast<uint2*>(out);
+  for (int64_t i = t; i < n4; i += stride) {
+    const float4 v = x4[i];
+    out2[i] = make_uint2(bf16_rne_bits(v.x) | (bf16_rne_bits(v.y) << 16),
+                         bf16_rne_bits(v.z) | (bf16_rne_bits(v.w) << 16));
+  }
+  for (int64_t i = 4 * n4 + t; i < n; i += stride)
+    out[i] = (bf16_t)bf16_rne_bits(x[i]);
 }
 
 // ============================ Philox keys ==============================
@@ -1564,6 +1592,24 @@ inline void check_f32(const at::Tensor& t, const char* name) {
               name, " must be contiguous fp32 CUDA tensor");
 }
 
+// Source operand of the gather kernels: fp32, or the bf16 copy made by
+// cast_bf16. Rows are read with 16-byte (8-byte) vector loads, so the
+// base must be aligned to that — true of every allocation, not of every
+// view of one.
+inline void check_src(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 2 &&
+                  (t.scalar_type() == at::kFloat ||
+                   t.scalar_type() == at::kBFloat16),
+              name, " must be a contiguous 2-D fp32 or bf16 CUDA tensor");
+  if (t.scalar_type() == at::kBFloat16)
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 8 == 0,
+                name, ": bf16 source must be 8-byte aligned");
+}
+
+const bf16_t* bf16_ptr(const at::Tensor& t) {
+  return reinterpret_cast<const bf16_t*>(t.data_ptr<at::BFloat16>());
+}
+
 const float* opt_ptr(const c10::optional<at::Tensor>& t) {
   return t.has_value() ? t->data_ptr<float>() : nullptr;
 }
@@ -1626,6 +1672,43 @@ void launch_worklist(K kernel, const WorkListArgs& w, int subw,
                      w.wl.end, w.wl.wave_start, args...);
 }
 
+// Kernel routing of spmm_sum for one source type. A bf16 source has the
+// F % 4 == 0 kernels only: other widths are upcast by the caller
+// (ops/functional.spmm_sum_raw) and take the fp32 route.
+template <typename T>
+void spmm_sum_route(const WorkListArgs& wl, const int32_t* indices,
+                    const T* x, const float* ss, const float* ds, float* out,
+                    int F, bool acc) {
+  // f4 <= this runs the half-wave variant
+  static const int subw32_max = env_int("BNSGCN_SPMM_SUBW32_MAX", 32);
+  // f4 <= this runs the edge-parallel narrow kernel (0 disables it)
+  static const int narrow_max =
+      std::min(env_int("BNSGCN_SPMM_NARROW_MAX", 16), 16);
+  auto launch = [&](auto kernel, int subw, int width) {
+    launch_worklist(kernel, wl, subw, indices, x, ss, ds, out, width);
+  };
+  if (F % 4 == 0 && F / 4 <= std::min(narrow_max, subw32_max))
+    launch(acc ? spmm_sum_narrow_kernel<T, true, 16>
+               : spmm_sum_narrow_kernel<T, false, 16>, 64, F / 4);
+  else if (F % 4 == 0 && F / 4 <= subw32_max)
+    launch(acc ? spmm_sum_vec4_kernel<T, true, 32>
+               : spmm_sum_vec4_kernel<T, false, 32>, 32, F / 4);
+  else if (F % 4 == 0)
+    launch(acc ? spmm_sum_vec4_kernel<T, true, 64>
+               : spmm_sum_vec4_kernel<T, false, 64>, 64, F / 4);
+  else if constexpr (std::is_same<T, float>::value) {
+    if (F % 2 == 0)
+      launch(acc ? spmm_sum_vec2_kernel<true> : spmm_sum_vec2_kernel<false>,
+             64, F / 2);
+    else
+      launch(acc ? spmm_sum_scalar_kernel<true>
+                 : spmm_sum_scalar_kernel<false>, 64, F);
+  } else {
+    TORCH_CHECK(false, "spmm_sum: a bf16 source covers F % 4 == 0, got F = ",
+                F);
+  }
+}
+
 at::Tensor spmm_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
                     at::Tensor wave_start, at::Tensor indices, at::Tensor x,
                     c10::optional<at::Tensor> src_scale,
@@ -1633,38 +1716,23 @@ at::Tensor spmm_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
                     at::Tensor out, bool acc) {
   // `out` is always caller-allocated: accumulate when acc, otherwise the
   // kernel overwrites every non-empty row (caller pre-zeroed split/empty
-  // rows — ops/csr_torch.build_worklist zero_rows).
-  check_f32(x, "x");
+  // rows — ops/csr_torch.build_worklist zero_rows). x is fp32 or bf16,
+  // out fp32 either way.
+  check_src(x, "x");
   check_f32(out, "out");
   TORCH_CHECK(indices.scalar_type() == at::kInt, "indices int32 expected");
   const WorkListArgs wl = worklist_args(wrow, wbeg, wend, wave_start);
   const int F = x.size(1);
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == F, "out: [n_rows, F] expected");
   if (wrow.numel() == 0 || wl.n_waves <= 0) return out;
-  // f4 <= this runs the half-wave variant
-  static const int subw32_max = env_int("BNSGCN_SPMM_SUBW32_MAX", 32);
-  // f4 <= this runs the edge-parallel narrow kernel (0 disables it)
-  static const int narrow_max =
-      std::min(env_int("BNSGCN_SPMM_NARROW_MAX", 16), 16);
-  auto launch = [&](auto kernel, int subw, int width) {
-    launch_worklist(kernel, wl, subw, indices.data_ptr<int32_t>(),
-                    x.data_ptr<float>(), opt_ptr(src_scale),
-                    opt_ptr(dst_scale), out.data_ptr<float>(), width);
-  };
-  if (F % 4 == 0 && F / 4 <= std::min(narrow_max, subw32_max))
-    launch(acc ? spmm_sum_narrow_kernel<true, 16>
-               : spmm_sum_narrow_kernel<false, 16>, 64, F / 4);
-  else if (F % 4 == 0 && F / 4 <= subw32_max)
-    launch(acc ? spmm_sum_vec4_kernel<true, 32>
-               : spmm_sum_vec4_kernel<false, 32>, 32, F / 4);
-  else if (F % 4 == 0)
-    launch(acc ? spmm_sum_vec4_kernel<true, 64>
-               : spmm_sum_vec4_kernel<false, 64>, 64, F / 4);
-  else if (F % 2 == 0)
-    launch(acc ? spmm_sum_vec2_kernel<true> : spmm_sum_vec2_kernel<false>,
-           64, F / 2);
+  if (x.scalar_type() == at::kBFloat16)
+    spmm_sum_route(wl, indices.data_ptr<int32_t>(), bf16_ptr(x),
+                   opt_ptr(src_scale), opt_ptr(dst_scale),
+                   out.data_ptr<float>(), F, acc);
   else
-    launch(acc ? spmm_sum_scalar_kernel<true> : spmm_sum_scalar_kernel<false>,
-           64, F);
+    spmm_sum_route(wl, indices.data_ptr<int32_t>(), x.data_ptr<float>(),
+                   opt_ptr(src_scale), opt_ptr(dst_scale),
+                   out.data_ptr<float>(), F, acc);
   return out;
 }
 
@@ -1672,23 +1740,35 @@ at::Tensor spmm_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
 // the format of ops/csr_torch.build_rowgroups — (wgroup, wbeg, wend,
 // wave_start) schedule the entries (ecol, ew[n_entries, R]); `out` is
 // caller-allocated with the builder's zero_rows pre-zeroed unless acc.
-template <int R>
+template <typename T, int R>
 void launch_grouped(const WorkListArgs& wl, bool acc, int f4,
                     const at::Tensor& ecol, const at::Tensor& ew,
-                    const at::Tensor& x, const float* ss, const float* ds,
+                    const T* x, const float* ss, const float* ds,
                     at::Tensor& out) {
   auto launch = [&](auto kernel) {
     launch_worklist(kernel, wl, 64, ecol.data_ptr<int32_t>(),
                     reinterpret_cast<const uint32_t*>(ew.data_ptr<uint8_t>()),
-                    x.data_ptr<float>(), ss, ds, out.data_ptr<float>(), f4,
-                    (int)out.size(0));
+                    x, ss, ds, out.data_ptr<float>(), f4, (int)out.size(0));
   };
   if (f4 > 64)                      // a second float4 per lane
-    launch(acc ? spmm_sum_grouped_kernel<true, R, 2>
-               : spmm_sum_grouped_kernel<false, R, 2>);
+    launch(acc ? spmm_sum_grouped_kernel<T, true, R, 2>
+               : spmm_sum_grouped_kernel<T, false, R, 2>);
   else
-    launch(acc ? spmm_sum_grouped_kernel<true, R, 1>
-               : spmm_sum_grouped_kernel<false, R, 1>);
+    launch(acc ? spmm_sum_grouped_kernel<T, true, R, 1>
+               : spmm_sum_grouped_kernel<T, false, R, 1>);
+}
+
+template <typename T>
+void route_grouped(int R, const WorkListArgs& wl, bool acc, int f4,
+                   const at::Tensor& ecol, const at::Tensor& ew, const T* x,
+                   const float* ss, const float* ds, at::Tensor& out) {
+  switch (R) {
+    case 4: launch_grouped<T, 4>(wl, acc, f4, ecol, ew, x, ss, ds, out); break;
+    case 8: launch_grouped<T, 8>(wl, acc, f4, ecol, ew, x, ss, ds, out); break;
+    // R = 16 was built and measured: slower than the per-row kernel at
+    // every gseg (profiles/BENCH_SUMMARY_rowgroup.md), so not instantiated
+    default: TORCH_CHECK(false, "spmm_sum_grouped: R must be 4 or 8, got ", R);
+  }
 }
 
 at::Tensor spmm_sum_grouped(at::Tensor wgroup, at::Tensor wbeg,
@@ -1697,7 +1777,7 @@ at::Tensor spmm_sum_grouped(at::Tensor wgroup, at::Tensor wbeg,
                             c10::optional<at::Tensor> src_scale,
                             c10::optional<at::Tensor> dst_scale,
                             at::Tensor out, bool acc) {
-  check_f32(x, "x");
+  check_src(x, "x");
   check_f32(out, "out");
   const WorkListArgs wl = worklist_args(wgroup, wbeg, wend, wave_start);
   TORCH_CHECK(ecol.scalar_type() == at::kInt && ecol.is_cuda() &&
@@ -1720,35 +1800,62 @@ at::Tensor spmm_sum_grouped(at::Tensor wgroup, at::Tensor wbeg,
   if (wgroup.numel() == 0 || wl.n_waves <= 0) return out;
   const float* ss = opt_ptr(src_scale);
   const float* ds = opt_ptr(dst_scale);
-  switch (R) {
-    case 4: launch_grouped<4>(wl, acc, F / 4, ecol, ew, x, ss, ds, out); break;
-    case 8: launch_grouped<8>(wl, acc, F / 4, ecol, ew, x, ss, ds, out); break;
-    // R = 16 was built and measured: slower than the per-row kernel at
-    // every gseg (profiles/BENCH_SUMMARY_rowgroup.md), so not instantiated
-    default: TORCH_CHECK(false, "spmm_sum_grouped: R must be 4 or 8, got ", R);
-  }
+  if (x.scalar_type() == at::kBFloat16)
+    route_grouped(R, wl, acc, F / 4, ecol, ew, bf16_ptr(x), ss, ds, out);
+  else
+    route_grouped(R, wl, acc, F / 4, ecol, ew, x.data_ptr<float>(), ss, ds,
+                  out);
   return out;
 }
 
-at::Tensor pack_rows(at::Tensor x, at::Tensor idx,
-                     c10::optional<at::Tensor> scale) {
-  check_f32(x, "x");
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
-  const int n = idx.numel(), F = x.size(1);
-  auto out = at::empty({n, F}, x.options());
-  if (n == 0) return out;
+template <typename T>
+void launch_pack(const T* x, const at::Tensor& idx, const float* scale,
+                 at::Tensor& out, int n, int F) {
   auto stream = at::cuda::getCurrentCUDAStream();
   const int64_t total = (int64_t)n * F;
   const int grid = std::min<int64_t>((total + 255) / 256, 4096);
   if (F % 4 == 0) {
-    hipLaunchKernelGGL(pack_rows_vec4_kernel, dim3(grid), dim3(256), 0, stream,
-                       x.data_ptr<float>(), idx.data_ptr<int64_t>(),
-                       opt_ptr(scale), out.data_ptr<float>(), n, F / 4);
+    hipLaunchKernelGGL(pack_rows_vec4_kernel<T>, dim3(grid), dim3(256), 0,
+                       stream, x, idx.data_ptr<int64_t>(), scale,
+                       out.data_ptr<float>(), n, F / 4);
   } else {
-    hipLaunchKernelGGL(pack_rows_kernel, dim3(grid), dim3(256), 0, stream,
-                       x.data_ptr<float>(), idx.data_ptr<int64_t>(),
-                       opt_ptr(scale), out.data_ptr<float>(), n, F);
+    hipLaunchKernelGGL(pack_rows_kernel<T>, dim3(grid), dim3(256), 0, stream,
+                       x, idx.data_ptr<int64_t>(), scale,
+                       out.data_ptr<float>(), n, F);
   }
+}
+
+at::Tensor pack_rows(at::Tensor x, at::Tensor idx,
+                     c10::optional<at::Tensor> scale) {
+  // x fp32 or bf16; the packed rows are fp32 either way
+  check_src(x, "x");
+  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
+  const int n = idx.numel(), F = x.size(1);
+  auto out = at::empty({n, F}, x.options().dtype(at::kFloat));
+  if (n == 0) return out;
+  if (x.scalar_type() == at::kBFloat16)
+    launch_pack(bf16_ptr(x), idx, opt_ptr(scale), out, n, F);
+  else
+    launch_pack(x.data_ptr<float>(), idx, opt_ptr(scale), out, n, F);
+  return out;
+}
+
+// fp32 -> bf16 copy, round to nearest even (cast_bf16_kernel).
+at::Tensor cast_bf16(at::Tensor x) {
+  check_f32(x, "x");
+  auto out = at::empty(x.sizes(), x.options().dtype(at::kBFloat16));
+  const int64_t n = x.numel();
+  if (n == 0) return out;
+  // the float4 / uint2 accesses need the bases aligned; `out` is a fresh
+  // allocation, x may be a view at an odd element offset
+  const bool aligned = reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0;
+  const int64_t n4 = aligned ? n / 4 : 0;
+  const int64_t threads = n4 + (n - 4 * n4);
+  const int grid = std::min<int64_t>((threads + 255) / 256, 8192);
+  hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid), dim3(256), 0,
+                     at::cuda::getCurrentCUDAStream(), x.data_ptr<float>(),
+                     reinterpret_cast<bf16_t*>(out.data_ptr<at::BFloat16>()),
+                     n, n4);
   return out;
 }
 
@@ -2263,6 +2370,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("spmm_sum_grouped", &spmm_sum_grouped,
         "row-group CSR SpMM sum with fused src/dst scales");
   m.def("pack_rows", &pack_rows, "gather rows + per-row scale");
+  m.def("cast_bf16", &cast_bf16, "fp32 -> bf16 copy, round to nearest even");
   m.def("scatter_add_rows", &scatter_add_rows, "scatter-add rows + scale");
   m.def("philox_keys", &philox_keys, "BNS sampling keys (Philox4x32-10)");
   m.def("syncbn_stats", &syncbn_stats, "column sum + sum of squares");

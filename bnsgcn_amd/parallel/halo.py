@@ -27,7 +27,8 @@ import os
 import torch
 from torch.autograd import Function
 
-from ..ops.functional import (pack_rows_raw, scatter_add_rows_raw, spmm_sum_raw)
+from ..ops.functional import (check_src_dtype, pack_rows_raw, round_bf16_raw,
+                              scatter_add_rows_raw, spmm_sum_raw)
 from .comm import all_to_all_rows
 from .plan import EpochState, HaloPlan
 from ..utils.timer import comm_timer
@@ -59,17 +60,32 @@ class _PartitionAggregate(Function):
                                + Σ_{r∈sampled halo rows→v} hscale[r]·recv[r] )
 
     recv = all-to-all of pack(x)·(1/ratio). hscale is the halo-side src
-    scale (GCN out-norm of the owning nodes; None for SAGE)."""
+    scale (GCN out-norm of the owning nodes; None for SAGE).
+
+    agg_dtype=torch.bfloat16 (--agg-dtype bf16): the source operand — x in
+    forward, g in backward — is rounded ONCE to bf16 and that one copy feeds
+    the pack, the inner SpMM and the halo-backward SpMM; everything after
+    the row read is fp32, and the backward is straight-through. The copy is
+    made on the main stream BEFORE the event the comm stream waits on.
+    Allocator lifetime: the copy belongs to the main stream's pool and is
+    read on the comm stream, with no record_stream — it stays referenced
+    until forward/backward returns, which is after the main stream has
+    waited on ev_done, recorded behind the comm stream's last read of it.
+    Whatever the main stream runs in a reused block is ordered after that
+    read, exactly as for x and g themselves."""
 
     @staticmethod
     def forward(ctx, x, plan: HaloPlan, st: EpochState,
                 inner_indptr, inner_indices, inner_t_indptr, inner_t_indices,
-                src_scale, dst_scale, use_halo_src_scale: bool):
+                src_scale, dst_scale, use_halo_src_scale: bool,
+                agg_dtype=None):
         # BNSGCN_NO_OVERLAP=1 disables the side-stream overlap (debug /
         # perf A/B); the sequential branch works for GPU tensors too.
         cuda = x.is_cuda and os.environ.get("BNSGCN_NO_OVERLAP") != "1"
 
         hscale = st.halo_out_norm_inv if use_halo_src_scale else None
+        if agg_dtype == torch.bfloat16:
+            x = round_bf16_raw(x)
         if cuda:
             cs = comm_stream()
             ev = torch.cuda.current_stream().record_event()
@@ -94,6 +110,7 @@ class _PartitionAggregate(Function):
             spmm_sum_raw(st.halo_fwd_indptr, st.halo_fwd_indices, recv,
                          src_scale=hscale, dst_scale=dst_scale, out=out)
         ctx.plan, ctx.st, ctx.hscale = plan, st, hscale
+        ctx.agg_dtype = agg_dtype
         ctx.save_for_backward(inner_t_indptr, inner_t_indices, src_scale, dst_scale)
         return out
 
@@ -103,6 +120,8 @@ class _PartitionAggregate(Function):
         inner_t_indptr, inner_t_indices, src_scale, dst_scale = ctx.saved_tensors
         hscale = ctx.hscale
         g = g.contiguous()
+        if ctx.agg_dtype == torch.bfloat16:
+            g = round_bf16_raw(g)
         cuda = g.is_cuda and os.environ.get("BNSGCN_NO_OVERLAP") != "1"
         if cuda:
             cs = comm_stream()
@@ -130,15 +149,17 @@ class _PartitionAggregate(Function):
             gx = spmm_sum_raw(inner_t_indptr, inner_t_indices, g,
                               src_scale=dst_scale, dst_scale=src_scale)
             scatter_add_rows_raw(gx, st.pack_idx, back, st.pack_scale)
-        return (gx,) + (None,) * 9
+        return (gx,) + (None,) * 10
 
 
 def partition_aggregate(x, plan: HaloPlan, inner_csrs, src_scale, dst_scale,
-                        use_halo_src_scale: bool):
-    """inner_csrs = (indptr, indices, indptr_T, indices_T) on device."""
+                        use_halo_src_scale: bool, agg_dtype=None):
+    """inner_csrs = (indptr, indices, indptr_T, indices_T) on device;
+    agg_dtype=torch.bfloat16 rounds the source operand to bf16."""
     ip, ix, tip, tix = inner_csrs
     return _PartitionAggregate.apply(x, plan, plan.state, ip, ix, tip, tix,
-                                     src_scale, dst_scale, use_halo_src_scale)
+                                     src_scale, dst_scale, use_halo_src_scale,
+                                     check_src_dtype(agg_dtype))
 
 
 class _HaloExchange(Function):

@@ -5,6 +5,7 @@ defaults, plus a few MI355X-framework extras (clearly marked).
 from __future__ import annotations
 
 import argparse
+import os
 
 
 def create_parser() -> argparse.ArgumentParser:
@@ -80,7 +81,30 @@ def create_parser() -> argparse.ArgumentParser:
                    default="fp32",
                    help="wire dtype for the per-layer halo all-to-all: bf16 "
                         "halves the xGMI bytes; compute stays fp32")
+    p.add_argument("--agg-dtype", "--agg_dtype", choices=["fp32", "bf16"],
+                   default=os.environ.get("BNSGCN_AGG_DTYPE", "fp32"),
+                   help="dtype of the source rows the GCN/SAGE aggregation "
+                        "gathers: bf16 rounds them once (forward and "
+                        "backward) and halves the bytes of every row read; "
+                        "scales, products, sums and outputs stay fp32. "
+                        "Default: $BNSGCN_AGG_DTYPE, else fp32")
     return p
+
+
+def agg_dtype_of(args):
+    """torch dtype of --agg-dtype for GraphContext.agg_dtype (None = fp32),
+    validated: the flag covers the GCN/SAGE aggregation only, so asking for
+    it with the GAT model is an error, never a silent no-op."""
+    import torch
+    name = getattr(args, "agg_dtype", "fp32")
+    if name not in ("fp32", "bf16"):
+        raise ValueError(f"--agg-dtype must be fp32 or bf16, got {name!r}")
+    if name == "bf16" and getattr(args, "model", None) == "gat":
+        raise ValueError(
+            "--agg-dtype bf16 covers the GCN/GraphSAGE aggregation only; the "
+            "GAT kernels are fp32. Use --agg-dtype fp32 (and unset "
+            "BNSGCN_AGG_DTYPE) with --model gat.")
+    return torch.bfloat16 if name == "bf16" else None
 
 
 def graph_name_of(args) -> str:

@@ -31,7 +31,7 @@ from ..models.models import create_model
 from ..ops.functional import pack_rows_raw, spmm_sum_raw
 from ..parallel import GradReducer, HaloPlan, all_to_all_rows, init_distributed
 from ..utils.timer import comm_timer
-from .config import graph_name_of
+from .config import agg_dtype_of, graph_name_of
 
 
 # --------------------------------------------------------------- offline
@@ -132,6 +132,7 @@ class RankState:
     """Everything one rank needs for the epoch loop."""
 
     def __init__(self, part: Partition, args, device):
+        agg_dtype = agg_dtype_of(args)      # raises on gat + bf16
         self.device = torch.device(device)
         self.part = part
         self.args = args
@@ -151,6 +152,7 @@ class RankState:
                              wire_dtype=wire)
         self.ctx = GraphContext.for_partition(part, self.plan, dev,
                                               need_eperm=(args.model == "gat"))
+        self.ctx.agg_dtype = agg_dtype
         self.halo_feat0 = None     # GAT use_pp layer-0 full halo features
         self.n_train_global = int(part.meta["n_train"])
         self.part_train = int(part.train_mask.sum())
@@ -224,6 +226,7 @@ class EvalState:
                              unit_ratio=True)
         self.plan.set_epoch(0)
         self.ctx = GraphContext.for_partition(part, self.plan, device)
+        self.ctx.agg_dtype = agg_dtype_of(args)
 
 
 @torch.no_grad()
@@ -333,6 +336,7 @@ class Evaluator:
         ctx = GraphContext.for_full_graph(
             torch.from_numpy(g.adj_in.indptr), torch.from_numpy(g.adj_in.indices),
             torch.from_numpy(g.in_deg), torch.from_numpy(g.out_deg), self.device)
+        ctx.agg_dtype = agg_dtype_of(self.args)
         feat = _feat_to_device(g.feat, self.device)
         label = torch.from_numpy(g.label).to(self.device)
         return ctx, feat, label, g
@@ -375,6 +379,7 @@ def run(args, rank: int | None = None, world_size: int | None = None) -> dict:
     # pin the device BEFORE the process group exists: an RCCL communicator
     # built while every rank still sits on cuda:0 is duplicate-device and
     # aborts the whole job (same guard as bench.py:88-96)
+    agg_dtype_of(args)      # --agg-dtype bf16 with GAT: fail at start-up
     pre_rank = int(os.environ.get("RANK", rank if rank is not None else 0))
     pre_world = int(os.environ.get("WORLD_SIZE",
                                    world_size if world_size is not None else 1))

@@ -11,7 +11,8 @@ import os
 
 import torch.multiprocessing as mp
 
-from bnsgcn_amd.runtime.config import create_parser, graph_name_of
+from bnsgcn_amd.runtime.config import (agg_dtype_of, create_parser,
+                                       graph_name_of)
 from bnsgcn_amd.runtime.trainer import prepare_partitions, run
 
 
@@ -26,6 +27,7 @@ def _worker(local_idx: int, start: int, world: int, args):
 
 def main():
     args = create_parser().parse_args()
+    agg_dtype_of(args)      # --agg-dtype bf16 + --model gat: fail before work
     args.graph_name = graph_name_of(args)
     if args.node_rank == 0 and not args.skip_partition:
         prepare_partitions(args)

@@ -22,6 +22,15 @@ row-group kernel for every (R, gseg): entries/edges, build time, format
 size and kernel time. --permute relabels the nodes with a random
 permutation first, which removes the id locality (the graph for finding
 the keep threshold GROUP_TAU).
+
+  python tools/spmm_micro.py --graph reddit --feats 44,128,256 \
+      --src-dtype fp32,bf16 [--grouped --group-r 4 --gseg 1024]
+
+--src-dtype times each listed source type on the same values: bf16 is the
+copy round_bf16_raw makes for --agg-dtype bf16 (the cast is not in the
+timed window). Every line then carries TB/s of requested rows: row reads
+(edges, or entries for the grouped kernel) x F x bytes per element of the
+source actually read, over the time of a call.
 """
 import argparse
 import os
@@ -34,7 +43,18 @@ import numpy as np
 import torch
 
 from bnsgcn_amd.graph import CSR
-from bnsgcn_amd.ops.functional import spmm_sum_raw
+from bnsgcn_amd.ops.functional import round_bf16_raw, spmm_sum_raw
+
+SRC_BYTES = {"fp32": 4, "bf16": 2}
+
+
+def source_of(x, src_dtype):
+    """x itself, or its bf16 copy; F % 4 != 0 has no bf16 kernel (the copy
+    is upcast again inside spmm_sum_raw), which the byte count follows."""
+    if src_dtype == "bf16":
+        xb = round_bf16_raw(x)
+        return xb, (2 if x.shape[1] % 4 == 0 else 4)
+    return x, 4
 
 
 def _relabel(src, dst, n, permute):
@@ -93,17 +113,18 @@ def device_csrs(c, train, which):
                                           ip.numel() - 1)]
 
 
-def grouped_table(label, ip, ix, n_src, F, a):
+def grouped_table(label, ip, ix, n_src, F, a, src_dtype="fp32"):
     """Per-row kernel against the row-group kernel on one CSR."""
     from bnsgcn_amd.ops.csr_torch import build_rowgroups
     e = ix.numel()
-    x = torch.randn(n_src, F, device="cuda")
+    x32 = torch.randn(n_src, F, device="cuda")
+    x, nbytes = source_of(x32, src_dtype)
     base = [time_call(lambda: spmm_sum_raw(ip, ix, x), a.iters)
             for _ in range(a.repeats)]
     med, spread = float(np.median(base)), max(base) - min(base)
-    print(f"{label} F={F} {e} edges: per-row {med*1e3:.3f} ms "
-          f"(spread {spread*1e3:.3f} over {a.repeats} x {a.iters})",
-          flush=True)
+    print(f"{label} F={F} src={src_dtype} {e} edges: per-row {med*1e3:.3f} ms "
+          f"(spread {spread*1e3:.3f} over {a.repeats} x {a.iters}), "
+          f"{e * F * nbytes / med / 1e12:.2f} TB/s requested", flush=True)
     for R in (int(r) for r in a.group_r.split(",")):
         for gseg in (int(g) for g in a.gseg.split(",")):
             torch.cuda.synchronize()
@@ -126,7 +147,8 @@ def grouped_table(label, ip, ix, n_src, F, a):
                   f"build {t_build*1e3:.0f} ms, {mb:.0f} MB, grouped "
                   f"{np.median(ts)*1e3:.3f} ms (spread "
                   f"{(max(ts)-min(ts))*1e3:.3f}), x{med/np.median(ts):.2f}, "
-                  f"max|diff|/max|ref| {err:.1e}", flush=True)
+                  f"{rg.ecol.numel() * F * nbytes / np.median(ts) / 1e12:.2f} "
+                  f"TB/s requested, max|diff|/max|ref| {err:.1e}", flush=True)
             del rg, ipg, ref, got
 
 
@@ -143,9 +165,14 @@ def main():
     p.add_argument("--group-r", default="4,8,16")
     p.add_argument("--gseg", default="512,1024,4096")
     p.add_argument("--repeats", type=int, default=3)
+    p.add_argument("--src-dtype", default="fp32",
+                   help="comma-separated subset of fp32,bf16: element type "
+                        "of the gathered source rows")
     p.add_argument("--permute", action="store_true",
                    help="relabel nodes randomly (no id locality)")
     a = p.parse_args()
+    src_dtypes = a.src_dtype.split(",")
+    assert all(d in SRC_BYTES for d in src_dtypes), a.src_dtype
     assert torch.cuda.is_available()
     c, train = (toy_csr if a.graph == "toy" else reddit_csr)(a.permute)
     for which in a.rows.split(","):
@@ -157,14 +184,22 @@ def main():
             e = ix.numel()
             for F in (int(f) for f in a.feats.split(",")):
                 if a.grouped:
-                    grouped_table(label, ip, ix, n_src, F, a)
+                    for sd in src_dtypes:
+                        grouped_table(label, ip, ix, n_src, F, a, sd)
                     continue
-                x = torch.randn(n_src, F, device="cuda")
-                dt = time_call(lambda: spmm_sum_raw(ip, ix, x), a.iters)
-                gb = e * F * 4 / 1e9
-                print(f"spmm {label} {e} edges F={F}: {dt*1e3:.3f} ms, "
-                      f"{gb/dt:.2f} GB/s logical", flush=True)
-                del x
+                x32 = torch.randn(n_src, F, device="cuda")
+                for sd in src_dtypes:
+                    x, nbytes = source_of(x32, sd)
+                    ts = [time_call(lambda: spmm_sum_raw(ip, ix, x), a.iters)
+                          for _ in range(a.repeats)]
+                    dt = float(np.median(ts))
+                    print(f"spmm {label} {e} edges F={F} src={sd}: "
+                          f"{dt*1e3:.3f} ms (spread "
+                          f"{(max(ts)-min(ts))*1e3:.3f} over {a.repeats} x "
+                          f"{a.iters}), {e * F * nbytes / dt / 1e12:.2f} TB/s "
+                          f"requested", flush=True)
+                    del x
+                del x32
 
 
 if __name__ == "__main__":
