@@ -61,6 +61,18 @@ def _projects_first(in_feats: int, out_feats: int) -> bool:
     return _pad4(out_feats) < in_feats
 
 
+def _gemm_bias(bias, defer_bias):
+    """The bias operand of a linear whose output goes straight into the
+    fused LayerNorm (F.layer_norm_act_dropout): with a `defer_bias` list
+    the parameter is appended to it and the GEMM gets bias.detach() — the
+    same forward, no column-sum kernel in the linear's backward; the fused
+    LayerNorm backward returns the gradient, colsum(dx), instead."""
+    if defer_bias is None or bias is None:
+        return bias
+    defer_bias.append(bias)
+    return bias.detach()
+
+
 class LayerNorm(nn.Module):
     """Drop-in affine nn.LayerNorm over the last dim: HIP ln_fwd/ln_bwd
     kernels on GPU (K7), torch on CPU. Same parameter names as
@@ -77,6 +89,12 @@ class LayerNorm(nn.Module):
     def forward(self, x, act: bool = False):
         """act=True fuses the following ReLU into the kernel pair (K9)."""
         return F.layer_norm(x, self.weight, self.bias, self.eps, act=act)
+
+    def forward_dropout(self, x, act: bool, p: float, bias_grad_to=()):
+        """dropout(self(x, act), p) of a training step on the fused kernel
+        pair; bias_grad_to as in F.layer_norm_act_dropout."""
+        return F.layer_norm_act_dropout(x, self.weight, self.bias, self.eps,
+                                        act, p, self.training, bias_grad_to)
 
 
 class Dropout(nn.Module):
@@ -104,19 +122,22 @@ class GCNLayer(nn.Module):
         if self.linear.bias is not None:
             _uniform_init(self.linear.bias, fan_in=in_feats)
 
-    def forward(self, ctx: GraphContext, x, rows: torch.Tensor | None = None):
+    def forward(self, ctx: GraphContext, x, rows: torch.Tensor | None = None,
+                defer_bias: list | None = None):
         """rows: final-layer loss-row restriction — output [len(rows), F]
-        (identical math for those rows; see GraphContext.aggregate)."""
+        (identical math for those rows; see GraphContext.aggregate).
+        defer_bias: see _gemm_bias."""
         if self.training and self.use_pp:
             if rows is not None:
                 x = x[rows]
-            return F.linear(x, self.linear.weight, self.linear.bias)
+            return F.linear(x, self.linear.weight,
+                            _gemm_bias(self.linear.bias, defer_bias))
         w, b = self.linear.weight, self.linear.bias
         if _projects_first(w.shape[1], w.shape[0]):
             h = _project_then_aggregate(ctx, x, w, "gcn", rows)
             return F.bias_add(h, b) if b is not None else h
         h = ctx.aggregate(x, "gcn", rows=rows)
-        return F.linear(h, w, b)
+        return F.linear(h, w, _gemm_bias(b, defer_bias))
 
 
 class SAGELayer(nn.Module):
@@ -140,12 +161,15 @@ class SAGELayer(nn.Module):
                 _uniform_init(self.linear1.bias, self.linear2.bias,
                               fan_in=in_feats)
 
-    def forward(self, ctx: GraphContext, x, rows: torch.Tensor | None = None):
+    def forward(self, ctx: GraphContext, x, rows: torch.Tensor | None = None,
+                defer_bias: list | None = None):
+        """defer_bias: see _gemm_bias."""
         if self.training and self.use_pp:
             # x = [feat ‖ precomputed neighbor mean], width 2F
             if rows is not None:
                 x = x[rows]
-            return F.linear(x, self.linear.weight, self.linear.bias)
+            return F.linear(x, self.linear.weight,
+                            _gemm_bias(self.linear.bias, defer_bias))
         x_dst = x[rows] if rows is not None else x
         if not self.use_pp:
             w2, b2 = self.linear2.weight, self.linear2.bias
@@ -157,8 +181,10 @@ class SAGELayer(nn.Module):
         if self.use_pp:  # eval path of a pp layer (reference layer.py:98-100)
             return F.linear(torch.cat((x_dst, ah), dim=1), self.linear.weight,
                             self.linear.bias)
-        return (F.linear(x_dst, self.linear1.weight, self.linear1.bias)
-                + F.linear(ah, self.linear2.weight, self.linear2.bias))
+        return (F.linear(x_dst, self.linear1.weight,
+                         _gemm_bias(self.linear1.bias, defer_bias))
+                + F.linear(ah, self.linear2.weight,
+                           _gemm_bias(self.linear2.bias, defer_bias)))
 
 
 class GATLayer(nn.Module):

@@ -14,6 +14,7 @@ from torch import nn
 
 import torch.nn.functional as TF
 
+from ..ops import functional as F
 from .context import GraphContext
 from .layers import GCNLayer, SAGELayer, GATLayer, LayerNorm, Dropout
 from .sync_bn import SyncBatchNorm
@@ -49,6 +50,23 @@ class GNNBase(nn.Module):
             h = self.activation(h)
         return h
 
+    def _fuses_post(self, i, h) -> bool:
+        """True if layer i's LayerNorm, ReLU and the dropout in front of
+        layer i+1 run as one kernel each way (_post_dropout) on layer i's
+        output, which lives where its input h lives."""
+        return (i < self.n_layers - 1 and self.use_norm
+                and isinstance(self.norm[i], LayerNorm)
+                and self.activation is TF.relu
+                and F.ln_fuse_active(h, self.norm[i].weight.numel(),
+                                     self.dropout.p, self.training))
+
+    def _post_dropout(self, i, h, biases):
+        """dropout(_post(i, h)) where _fuses_post holds. The dropout seed
+        is drawn here, after layer i and before anything of layer i+1, so
+        the draws keep their order and every mask is the unfused one.
+        `biases`: the bias parameters layer i deferred to this op."""
+        return self.norm[i].forward_dropout(h, True, self.dropout.p, biases)
+
 
 class GCN(GNNBase):
     conv_cls = GCNLayer
@@ -75,15 +93,24 @@ class GCN(GNNBase):
         RNG draws match the unrestricted run."""
         h = feat
         restrict = self.training and getattr(ctx, "loss_rows", None) is not None
+        dropped = False     # h already went through the next layer's dropout
         for i in range(self.n_layers):
             rows = ctx.loss_rows if (restrict and i == self.n_layers - 1) \
                 else None
-            h = self.dropout(h)
-            if i < self.n_layers - self.n_linear:
-                h = self.layers[i](ctx, h, rows=rows)
+            if not dropped:
+                h = self.dropout(h)
+            lay = self.layers[i]
+            conv = i < self.n_layers - self.n_linear
+            dropped = self._fuses_post(i, h)
+            # on the fused path the conv layer's GEMM biases get their
+            # gradient from the LayerNorm backward (layers._gemm_bias)
+            biases = [] if (dropped and conv) else None
+            if conv:
+                h = lay(ctx, h, rows=rows, defer_bias=biases)
             else:
-                h = self.layers[i](h[rows] if rows is not None else h)
-            h = self._post(i, h)
+                h = lay(h[rows] if rows is not None else h)
+            h = self._post_dropout(i, h, biases or ()) if dropped \
+                else self._post(i, h)
         return h
 
 

@@ -553,6 +553,68 @@ def dropout(x, p: float, training: bool):
     return torch.nn.functional.dropout(x, p, training)
 
 
+# Fused LayerNorm + ReLU + dropout between the layers (ln_act_drop_fwd /
+# ln_act_drop_bwd). BNSGCN_LN_FUSE=0 (or setting _LN_FUSE False) keeps the
+# separate layer_norm and dropout ops: the same masks and the same forward
+# bits, three more passes over the activation per layer in each direction.
+_LN_FUSE = _os.environ.get("BNSGCN_LN_FUSE", "1") != "0"
+
+
+def ln_fuse_active(x, width: int, p: float, training: bool) -> bool:
+    """True where layer_norm_act_dropout runs the fused kernels on a
+    [*, width] activation that lives where x lives: HIP, fp32, width <=
+    1024, training with p > 0. The models ask BEFORE the layer runs, since
+    on this path the layer hands its bias gradients to the fused op."""
+    return (_LN_FUSE and training and p > 0.0 and width <= 1024
+            and x.dim() == 2 and x.dtype == torch.float32 and use_hip(x))
+
+
+class _LayerNormActDropoutF(Function):
+    """y = dropout(act(LN(x))) in one kernel, and the whole backward in
+    one pass: dx, dgamma, dbeta and colsum(dx). `biases` are the bias
+    parameters that the linears producing x added to every row of it;
+    their values are not read, and their gradient is colsum(dx) by the
+    chain rule — the caller passes bias.detach() to those linears so that
+    nothing else computes it."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, act, keep, seed, *biases):
+        x = x.contiguous()
+        y, mean, rstd = get_ext().ln_act_drop_fwd(x, weight, bias, eps,
+                                                  int(act), keep, seed)
+        ctx.save_for_backward(x, weight, bias, mean, rstd)
+        ctx.act, ctx.keep, ctx.seed = int(act), keep, seed
+        ctx.n_biases = len(biases)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, b, mean, rstd = ctx.saved_tensors
+        dx, dw, db, colsum = get_ext().ln_act_drop_bwd(
+            x, dy.contiguous(), w, b, mean, rstd, ctx.act, ctx.keep, ctx.seed)
+        # one tensor per parameter: .grad of two parameters never aliases
+        gb = tuple(colsum if i == 0 else colsum.clone()
+                   for i in range(ctx.n_biases))
+        return (dx, dw, db, None, None, None, None) + gb
+
+
+def layer_norm_act_dropout(x, weight, bias, eps: float = 1e-5,
+                           act: bool = False, p: float = 0.0,
+                           training: bool = False, bias_grad_to=()):
+    """dropout(layer_norm(x, act=act), p, training), fused into one kernel
+    each way where ln_fuse_active(x, ...) holds; the seed is drawn exactly
+    as dropout() draws it, so the mask is the unfused one. bias_grad_to:
+    see _LayerNormActDropoutF — only valid on the fused path."""
+    if ln_fuse_active(x, x.shape[-1], p, training):
+        seed = int(torch.randint(0, 2**62, (1,)).item())
+        return _LayerNormActDropoutF.apply(x, weight, bias, eps, act,
+                                           1.0 - p, seed, *bias_grad_to)
+    if len(bias_grad_to):
+        raise RuntimeError("layer_norm_act_dropout: bias_grad_to needs the "
+                           "fused path (ln_fuse_active)")
+    return dropout(layer_norm(x, weight, bias, eps, act), p, training)
+
+
 def segment_softmax2_raw(indptr1, logits1, indptr2, logits2):
     if use_hip(logits1):
         return get_ext().segment_softmax2(indptr1, logits1, indptr2, logits2,

@@ -1345,11 +1345,41 @@ __global__ void attn_project_dattn_kernel(
 // writes max(ln, 0); backward recomputes the pre-activation from
 // (x, mean, rstd, gamma, beta) and masks dy — no mask storage, no
 // separate ReLU kernels (K9).
-__global__ __launch_bounds__(256) void ln_fwd_kernel(
+//
+// The plain kernels (ln_fwd / ln_bwd) and their fused siblings
+// (ln_act_drop_fwd / _bwd, which add the inter-layer dropout and, backward,
+// the column sums) take their row arithmetic from the SAME DEV_INLINE
+// functions: the scalar pairs share a whole body behind a template flag,
+// the float4 pairs share the per-chunk functions (ln_out4, ln_dx4, ...).
+// The fused results must equal the unfused composition bit for bit — the
+// pre-activation's sign decides ReLU mask bits. Sharing the source is not
+// enough for that: left to itself the compiler contracts a * b + c into an
+// fma or not depending on the code around it (the unrolled fused forward
+// folded mu = s / F into every x - mu, the plain one did not). So these
+// functions and the kernels that call them switch contraction off (LN_EXACT)
+// and spell out each fma, in the form the plain kernels have always had.
+#define LN_EXACT _Pragma("clang fp contract(off)")
+// The fused kernels are built without the packed fp32 VALU instructions:
+// one scalar instruction per element, as the explicit arithmetic reads.
+#define LN_NO_PK __attribute__((target("no-packed-fp32-ops")))
+
+// Dropout of the fused pair, as dropout_apply_kernel decides it: off for
+// keep >= 1, element index the flat r * F + f.
+struct LnDrop {
+  bool on; uint32_t thr; float inv_keep; uint64_t seed;
+};
+DEV_INLINE LnDrop ln_drop(float keep, uint64_t seed) {
+  const bool on = keep < 1.0f;
+  return {on, drop_threshold(keep), on ? 1.0f / keep : 1.0f, seed};
+}
+
+template <bool DROP>
+DEV_INLINE void ln_fwd_rows(
     const float* __restrict__ x, const float* __restrict__ gamma,
     const float* __restrict__ beta, float* __restrict__ y,
     float* __restrict__ mean_out, float* __restrict__ rstd_out,
-    int64_t n, int F, float eps, int act) {
+    int64_t n, int F, float eps, int act, LnDrop dp) {
+  LN_EXACT
   const int lane = threadIdx.x & 63;
   const float inv_f = 1.0f / F;
   float vals[LN_MAX_K], gm[LN_MAX_K], bt[LN_MAX_K];
@@ -1365,14 +1395,17 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(
     s = wave_reduce_sum(s);
     const float mu = s * inv_f;
     float v = 0.f;
-    for (int i = 0; i < K; ++i) { const float d = vals[i] - mu; v += d * d; }
+    for (int i = 0; i < K; ++i) { const float d = vals[i] - mu; v = fmaf(d, d, v); }
     v = wave_reduce_sum(v);
-    const float rstd = rsqrtf(v * inv_f + eps);
+    const float rstd = rsqrtf(fmaf(v, inv_f, eps));
     float* yr = y + r * (int64_t)F;
     k = 0;
     for (int f = lane; f < F; f += WAVE, ++k) {
-      const float o = (vals[k] - mu) * rstd * gm[k] + bt[k];
-      yr[f] = act ? fmaxf(o, 0.f) : o;
+      float o = fmaf((vals[k] - mu) * rstd, gm[k], bt[k]);
+      if (act) o = fmaxf(o, 0.f);
+      if (DROP && dp.on)
+        o = drop_apply(o, r * (int64_t)F + f, dp.thr, dp.seed, dp.inv_keep);
+      yr[f] = o;
     }
     if (lane == 0) { mean_out[r] = mu; rstd_out[r] = rstd; }
   }
@@ -1381,11 +1414,70 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(
 // float4 variants (F % 4 == 0): lane l covers float4 chunks l, l+64, ...
 // — 16 B loads instead of 4 B (the scalar LN backward measured 2.8 TB/s
 // on [2.45M, 128]; products profile topk_products_final_r02.txt)
+// The arithmetic of one float4 chunk, shared by the plain kernels (chunk
+// loops of run-time length) and the fused ones (unrolled KV times).
+DEV_INLINE float ln_sum4(float4 v) {
+  LN_EXACT
+  return v.x + v.y + v.z + v.w;
+}
+DEV_INLINE float ln_dot4(float4 u, float4 v) {
+  LN_EXACT
+  return u.x * v.x + u.y * v.y + u.z * v.z + u.w * v.w;
+}
+DEV_INLINE float ln_sqdev4(float4 v, float mu) {
+  LN_EXACT
+  const float a = v.x - mu, b = v.y - mu;
+  const float c = v.z - mu, d = v.w - mu;
+  return a * a + b * b + c * c + d * d;
+}
+DEV_INLINE float4 ln_out4(float4 v, float mu, float rstd, float4 gm,
+                          float4 bt, int act) {
+  LN_EXACT
+  float4 o;
+  o.x = fmaf((v.x - mu) * rstd, gm.x, bt.x);
+  o.y = fmaf((v.y - mu) * rstd, gm.y, bt.y);
+  o.z = fmaf((v.z - mu) * rstd, gm.z, bt.z);
+  o.w = fmaf((v.w - mu) * rstd, gm.w, bt.w);
+  if (act) {
+    o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f);
+    o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
+  }
+  return o;
+}
+DEV_INLINE float4 ln_xhat4(float4 xv, float mu, float rs) {
+  LN_EXACT
+  return make_float4((xv.x - mu) * rs, (xv.y - mu) * rs, (xv.z - mu) * rs,
+                     (xv.w - mu) * rs);
+}
+// dy where the recomputed pre-activation is positive, else 0
+DEV_INLINE float4 ln_relu_mask4(float4 dv, float4 xh, float4 gm, float4 bt) {
+  LN_EXACT
+  if (fmaf(xh.x, gm.x, bt.x) <= 0.f) dv.x = 0.f;
+  if (fmaf(xh.y, gm.y, bt.y) <= 0.f) dv.y = 0.f;
+  if (fmaf(xh.z, gm.z, bt.z) <= 0.f) dv.z = 0.f;
+  if (fmaf(xh.w, gm.w, bt.w) <= 0.f) dv.w = 0.f;
+  return dv;
+}
+DEV_INLINE float4 ln_mul4(float4 u, float4 v) {
+  LN_EXACT
+  return make_float4(u.x * v.x, u.y * v.y, u.z * v.z, u.w * v.w);
+}
+DEV_INLINE float4 ln_dx4(float4 g, float4 xh, float a, float b, float rs) {
+  LN_EXACT
+  float4 o;
+  o.x = rs * fmaf(-xh.x, b, g.x - a);
+  o.y = rs * fmaf(-xh.y, b, g.y - a);
+  o.z = rs * fmaf(-xh.z, b, g.z - a);
+  o.w = rs * fmaf(-xh.w, b, g.w - a);
+  return o;
+}
+
 __global__ __launch_bounds__(256) void ln_fwd_v4_kernel(
     const float4* __restrict__ x, const float4* __restrict__ gamma,
     const float4* __restrict__ beta, float4* __restrict__ y,
     float* __restrict__ mean_out, float* __restrict__ rstd_out,
     int64_t n, int F, float eps, int act) {
+  LN_EXACT
   const int lane = threadIdx.x & 63;
   const int F4 = F >> 2;
   const float inv_f = 1.0f / F;
@@ -1400,34 +1492,154 @@ __global__ __launch_bounds__(256) void ln_fwd_v4_kernel(
     int k = 0;
     for (int f = lane; f < F4; f += WAVE, ++k) {
       vals[k] = xr[f];
-      s += vals[k].x + vals[k].y + vals[k].z + vals[k].w;
+      s += ln_sum4(vals[k]);
     }
     s = wave_reduce_sum(s);
     const float mu = s * inv_f;
     float v = 0.f;
-    for (int i = 0; i < K; ++i) {
-      const float a = vals[i].x - mu, b = vals[i].y - mu;
-      const float c = vals[i].z - mu, d = vals[i].w - mu;
-      v += a * a + b * b + c * c + d * d;
-    }
+    for (int i = 0; i < K; ++i) v += ln_sqdev4(vals[i], mu);
     v = wave_reduce_sum(v);
-    const float rstd = rsqrtf(v * inv_f + eps);
+    const float rstd = rsqrtf(fmaf(v, inv_f, eps));
     float4* yr = y + r * F4;
     k = 0;
-    for (int f = lane; f < F4; f += WAVE, ++k) {
-      float4 o;
-      o.x = (vals[k].x - mu) * rstd * gm[k].x + bt[k].x;
-      o.y = (vals[k].y - mu) * rstd * gm[k].y + bt[k].y;
-      o.z = (vals[k].z - mu) * rstd * gm[k].z + bt[k].z;
-      o.w = (vals[k].w - mu) * rstd * gm[k].w + bt[k].w;
-      if (act) {
-        o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f);
-        o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
+    for (int f = lane; f < F4; f += WAVE, ++k)
+      yr[f] = ln_out4(vals[k], mu, rstd, gm[k], bt[k], act);
+    if (lane == 0) { mean_out[r] = mu; rstd_out[r] = rstd; }
+  }
+}
+
+// y = dropout(act(LN(x))): what ln_fwd followed by dropout_apply writes,
+// without the pass that re-reads and re-writes y. KV = float4 chunks per
+// lane (F <= 256 * KV), a compile-time bound so that the row stays in
+// registers: the run-time chunk loops of the plain kernels index their
+// arrays dynamically and spill them to scratch.
+template <int KV>
+LN_NO_PK __global__ __launch_bounds__(256) void ln_act_drop_fwd_v4_kernel(
+    const float4* __restrict__ x, const float4* __restrict__ gamma,
+    const float4* __restrict__ beta, float4* __restrict__ y,
+    float* __restrict__ mean_out, float* __restrict__ rstd_out,
+    int64_t n, int F, float eps, int act, float keep, uint64_t seed) {
+  LN_EXACT
+  const int lane = threadIdx.x & 63;
+  const int F4 = F >> 2;
+  const float inv_f = 1.0f / F;
+  const LnDrop dp = ln_drop(keep, seed);
+  float4 vals[KV], gm[KV], bt[KV];
+#pragma unroll
+  for (int k = 0; k < KV; ++k) {
+    const int f = lane + k * WAVE;
+    if (f < F4) { gm[k] = gamma[f]; bt[k] = beta[f]; }
+  }
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n;
+       r += stride) {
+    const float4* xr = x + r * F4;
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+      const int f = lane + k * WAVE;
+      if (f < F4) { vals[k] = xr[f]; s += ln_sum4(vals[k]); }
+    }
+    s = wave_reduce_sum(s);
+    const float mu = s * inv_f;
+    float v = 0.f;
+#pragma unroll
+    for (int k = 0; k < KV; ++k)
+      if (lane + k * WAVE < F4) v += ln_sqdev4(vals[k], mu);
+    v = wave_reduce_sum(v);
+    const float rstd = rsqrtf(fmaf(v, inv_f, eps));
+    float4* yr = y + r * F4;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+      const int f = lane + k * WAVE;
+      if (f < F4) {
+        float4 o = ln_out4(vals[k], mu, rstd, gm[k], bt[k], act);
+        if (dp.on)
+          o = drop_apply(o, (r * F4 + f) * 4, dp.thr, dp.seed, dp.inv_keep);
+        yr[f] = o;
       }
-      yr[f] = o;
     }
     if (lane == 0) { mean_out[r] = mu; rstd_out[r] = rstd; }
   }
+}
+
+__global__ __launch_bounds__(256) void ln_fwd_kernel(
+    const float* __restrict__ x, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float* __restrict__ y,
+    float* __restrict__ mean_out, float* __restrict__ rstd_out,
+    int64_t n, int F, float eps, int act) {
+  ln_fwd_rows<false>(x, gamma, beta, y, mean_out, rstd_out, n, F, eps, act,
+                     LnDrop{});
+}
+
+LN_NO_PK __global__ __launch_bounds__(256) void ln_act_drop_fwd_kernel(
+    const float* __restrict__ x, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float* __restrict__ y,
+    float* __restrict__ mean_out, float* __restrict__ rstd_out,
+    int64_t n, int F, float eps, int act, float keep, uint64_t seed) {
+  ln_fwd_rows<true>(x, gamma, beta, y, mean_out, rstd_out, n, F, eps, act,
+                    ln_drop(keep, seed));
+}
+
+// Column sums of the fused backward. A lane owns the same columns in every
+// row its wave walks, so dgamma, dbeta and colsum(dx) are running sums in
+// registers over the grid-stride loop; ln_colsum_store then adds the four
+// waves of the block in wave order through LDS (3 * F floats) and writes
+// ONE partial row [3, F] per block. ln_colsum_finish_kernel reduces the
+// partial rows. Partial rows and not atomics: every sum is taken in a
+// fixed order, so two runs give the same bits (the atomic ln_bwd_w_kernel
+// does not), and at most LN_FUSED_BLOCKS rows of 3 * F floats are written
+// and read once — 6 MB against the 717 MB the pass moves at [232965, 256].
+#define LN_FUSED_BLOCKS 2048
+
+template <int NV>
+DEV_INLINE void ln_colsum_store(const float (&sg)[NV], const float (&sb)[NV],
+                                const float (&sc)[NV], int F, int vec,
+                                float* __restrict__ partial) {
+  // value i of the lane's arrays is column (i / vec * WAVE + lane) * vec +
+  // i % vec: vec = 4 for the float4 kernels, 1 for the scalar ones
+  extern __shared__ float ln_red[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int w = 0; w < 4; ++w) {
+    if (wave == w) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int c = ((i / vec) * WAVE + lane) * vec + i % vec;
+        if (c < F) {
+          if (w == 0) {
+            ln_red[c] = sg[i]; ln_red[F + c] = sb[i]; ln_red[2 * F + c] = sc[i];
+          } else {
+            ln_red[c] += sg[i]; ln_red[F + c] += sb[i];
+            ln_red[2 * F + c] += sc[i];
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  float* prow = partial + (int64_t)blockIdx.x * 3 * F;
+  for (int j = threadIdx.x; j < 3 * F; j += blockDim.x) prow[j] = ln_red[j];
+}
+
+// out[j] = sum over the nb partial rows of column j (j < C = 3 * F). A
+// block takes 16 columns; thread (ty, tx) adds rows ty, ty + 16, ... of
+// column tx in order, then the 16 row lanes combine in a fixed tree.
+LN_NO_PK __global__ __launch_bounds__(256) void ln_colsum_finish_kernel(
+    const float* __restrict__ partial, float* __restrict__ out, int nb,
+    int C) {
+  __shared__ float red[16][17];
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int c = blockIdx.x * 16 + tx;
+  float s = 0.f;
+  if (c < C)
+    for (int r = ty; r < nb; r += 16) s += partial[(int64_t)r * C + c];
+  red[ty][tx] = s;
+  __syncthreads();
+  for (int h = 8; h > 0; h >>= 1) {
+    if (ty < h) red[ty][tx] += red[ty + h][tx];
+    __syncthreads();
+  }
+  if (ty == 0 && c < C) out[c] = red[0][tx];
 }
 
 __global__ __launch_bounds__(256) void ln_bwd_dx_v4_kernel(
@@ -1435,6 +1647,7 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_v4_kernel(
     const float4* __restrict__ gamma, const float4* __restrict__ beta,
     const float* __restrict__ mean, const float* __restrict__ rstd,
     float4* __restrict__ dx, int64_t n, int F, int act) {
+  LN_EXACT
   const int lane = threadIdx.x & 63;
   const int F4 = F >> 2;
   const float inv_f = 1.0f / F;
@@ -1454,47 +1667,108 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_v4_kernel(
     float a = 0.f, b = 0.f;
     int k = 0;
     for (int f = lane; f < F4; f += WAVE, ++k) {
-      const float4 xv = xr[f];
       float4 dv = dr[f];
-      xh[k].x = (xv.x - mu) * rs; xh[k].y = (xv.y - mu) * rs;
-      xh[k].z = (xv.z - mu) * rs; xh[k].w = (xv.w - mu) * rs;
-      if (act) {
-        if (xh[k].x * gm[k].x + bt[k].x <= 0.f) dv.x = 0.f;
-        if (xh[k].y * gm[k].y + bt[k].y <= 0.f) dv.y = 0.f;
-        if (xh[k].z * gm[k].z + bt[k].z <= 0.f) dv.z = 0.f;
-        if (xh[k].w * gm[k].w + bt[k].w <= 0.f) dv.w = 0.f;
-      }
-      g[k].x = dv.x * gm[k].x; g[k].y = dv.y * gm[k].y;
-      g[k].z = dv.z * gm[k].z; g[k].w = dv.w * gm[k].w;
-      a += g[k].x + g[k].y + g[k].z + g[k].w;
-      b += g[k].x * xh[k].x + g[k].y * xh[k].y + g[k].z * xh[k].z +
-           g[k].w * xh[k].w;
+      xh[k] = ln_xhat4(xr[f], mu, rs);
+      if (act) dv = ln_relu_mask4(dv, xh[k], gm[k], bt[k]);
+      g[k] = ln_mul4(dv, gm[k]);
+      a += ln_sum4(g[k]);
+      b += ln_dot4(g[k], xh[k]);
     }
     a = wave_reduce_sum(a) * inv_f;
     b = wave_reduce_sum(b) * inv_f;
     float4* dxr = dx + r * F4;
     k = 0;
-    for (int f = lane; f < F4; f += WAVE, ++k) {
-      float4 o;
-      o.x = rs * (g[k].x - a - xh[k].x * b);
-      o.y = rs * (g[k].y - a - xh[k].y * b);
-      o.z = rs * (g[k].z - a - xh[k].z * b);
-      o.w = rs * (g[k].w - a - xh[k].w * b);
-      dxr[f] = o;
+    for (int f = lane; f < F4; f += WAVE, ++k)
+      dxr[f] = ln_dx4(g[k], xh[k], a, b, rs);
+  }
+}
+
+// The whole backward of y = dropout(act(LN(x))) in one pass over x and dy:
+// dy gets the regenerated dropout mask and 1/keep as it is loaded, then
+// the arithmetic of ln_bwd_dx_v4_kernel gives dx, and dgamma, dbeta and
+// colsum(dx) — the bias gradient of the linears that produced x —
+// accumulate per lane (ln_colsum_store). KV as in the forward.
+template <int KV>
+LN_NO_PK __global__ __launch_bounds__(256) void ln_act_drop_bwd_v4_kernel(
+    const float4* __restrict__ x, const float4* __restrict__ dy,
+    const float4* __restrict__ gamma, const float4* __restrict__ beta,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    float4* __restrict__ dx, float* __restrict__ partial, int64_t n, int F,
+    int act, float keep, uint64_t seed) {
+  LN_EXACT
+  const int lane = threadIdx.x & 63;
+  const int F4 = F >> 2;
+  const float inv_f = 1.0f / F;
+  const LnDrop dp = ln_drop(keep, seed);
+  float4 xh[KV], g[KV], gm[KV], bt[KV];
+  float sg[4 * KV] = {}, sb[4 * KV] = {}, sc[4 * KV] = {};
+#pragma unroll
+  for (int k = 0; k < KV; ++k) {
+    const int f = lane + k * WAVE;
+    if (f < F4) {
+      gm[k] = gamma[f];
+      if (act) bt[k] = beta[f];
     }
   }
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n;
+       r += stride) {
+    const float4* xr = x + r * F4;
+    const float4* dr = dy + r * F4;
+    const float mu = mean[r], rs = rstd[r];
+    float a = 0.f, b = 0.f;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+      const int f = lane + k * WAVE;
+      if (f < F4) {
+        float4 dv = dr[f];
+        if (dp.on)
+          dv = drop_apply(dv, (r * F4 + f) * 4, dp.thr, dp.seed, dp.inv_keep);
+        xh[k] = ln_xhat4(xr[f], mu, rs);
+        if (act) dv = ln_relu_mask4(dv, xh[k], gm[k], bt[k]);
+        g[k] = ln_mul4(dv, gm[k]);
+        a += ln_sum4(g[k]);
+        b += ln_dot4(g[k], xh[k]);
+        sg[4 * k + 0] += dv.x * xh[k].x; sg[4 * k + 1] += dv.y * xh[k].y;
+        sg[4 * k + 2] += dv.z * xh[k].z; sg[4 * k + 3] += dv.w * xh[k].w;
+        sb[4 * k + 0] += dv.x; sb[4 * k + 1] += dv.y;
+        sb[4 * k + 2] += dv.z; sb[4 * k + 3] += dv.w;
+      }
+    }
+    a = wave_reduce_sum(a) * inv_f;
+    b = wave_reduce_sum(b) * inv_f;
+    float4* dxr = dx + r * F4;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+      const int f = lane + k * WAVE;
+      if (f < F4) {
+        const float4 o = ln_dx4(g[k], xh[k], a, b, rs);
+        dxr[f] = o;
+        sc[4 * k + 0] += o.x; sc[4 * k + 1] += o.y;
+        sc[4 * k + 2] += o.z; sc[4 * k + 3] += o.w;
+      }
+    }
+  }
+  ln_colsum_store<4 * KV>(sg, sb, sc, F, 4, partial);
 }
 
 // dx = rstd * ( g - mean(g) - xhat * mean(g * xhat) ),  g = dy * gamma
 // (act=1: g is first masked by the recomputed pre-activation sign)
-__global__ __launch_bounds__(256) void ln_bwd_dx_kernel(
+// FUSED (the scalar ln_act_drop_bwd) adds the dropout of dy and the column
+// sums around the same statements.
+template <bool FUSED>
+DEV_INLINE void ln_bwd_rows(
     const float* __restrict__ x, const float* __restrict__ dy,
     const float* __restrict__ gamma, const float* __restrict__ beta,
     const float* __restrict__ mean, const float* __restrict__ rstd,
-    float* __restrict__ dx, int64_t n, int F, int act) {
+    float* __restrict__ dx, int64_t n, int F, int act, LnDrop dp,
+    float* __restrict__ partial) {
+  LN_EXACT
   const int lane = threadIdx.x & 63;
   const float inv_f = 1.0f / F;
   float xh[LN_MAX_K], g[LN_MAX_K], gm[LN_MAX_K], bt[LN_MAX_K];
+  float sg[FUSED ? LN_MAX_K : 1] = {}, sb[FUSED ? LN_MAX_K : 1] = {};
+  float sc[FUSED ? LN_MAX_K : 1] = {};
   int K = 0;
   for (int f = lane; f < F; f += WAVE, ++K) {
     gm[K] = gamma[f];
@@ -1511,18 +1785,44 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_kernel(
     for (int f = lane; f < F; f += WAVE, ++k) {
       xh[k] = (xr[f] - mu) * rs;
       float d = dr[f];
-      if (act && xh[k] * gm[k] + bt[k] <= 0.f) d = 0.f;
+      if (FUSED && dp.on)
+        d = drop_apply(d, r * (int64_t)F + f, dp.thr, dp.seed, dp.inv_keep);
+      if (act && fmaf(xh[k], gm[k], bt[k]) <= 0.f) d = 0.f;
       g[k] = d * gm[k];
       a += g[k];
       b += g[k] * xh[k];
+      if (FUSED) { sg[k] += d * xh[k]; sb[k] += d; }
     }
     a = wave_reduce_sum(a) * inv_f;
     b = wave_reduce_sum(b) * inv_f;
     float* dxr = dx + r * (int64_t)F;
     k = 0;
-    for (int f = lane; f < F; f += WAVE, ++k)
-      dxr[f] = rs * (g[k] - a - xh[k] * b);
+    for (int f = lane; f < F; f += WAVE, ++k) {
+      const float o = rs * fmaf(-xh[k], b, g[k] - a);
+      dxr[f] = o;
+      if (FUSED) sc[k] += o;
+    }
   }
+  if (FUSED) ln_colsum_store<FUSED ? LN_MAX_K : 1>(sg, sb, sc, F, 1, partial);
+}
+
+__global__ __launch_bounds__(256) void ln_bwd_dx_kernel(
+    const float* __restrict__ x, const float* __restrict__ dy,
+    const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    float* __restrict__ dx, int64_t n, int F, int act) {
+  ln_bwd_rows<false>(x, dy, gamma, beta, mean, rstd, dx, n, F, act, LnDrop{},
+                     nullptr);
+}
+
+LN_NO_PK __global__ __launch_bounds__(256) void ln_act_drop_bwd_kernel(
+    const float* __restrict__ x, const float* __restrict__ dy,
+    const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    float* __restrict__ dx, float* __restrict__ partial, int64_t n, int F,
+    int act, float keep, uint64_t seed) {
+  ln_bwd_rows<true>(x, dy, gamma, beta, mean, rstd, dx, n, F, act,
+                    ln_drop(keep, seed), partial);
 }
 
 // dgamma[f] = sum_r dy*xhat, dbeta[f] = sum_r dy — column reduction in
@@ -1973,6 +2273,113 @@ std::vector<at::Tensor> ln_bwd(at::Tensor x, at::Tensor dy, at::Tensor gamma,
   return {dx, dw[0], dw[1]};
 }
 
+// float4 chunks per lane of the fused LayerNorm kernels: F <= 256 * KV
+#define LN_KV_DISPATCH(F, ...)                                      \
+  do {                                                              \
+    if ((F) <= 256) { constexpr int KV = 1; __VA_ARGS__; }          \
+    else if ((F) <= 512) { constexpr int KV = 2; __VA_ARGS__; }     \
+    else if ((F) <= 768) { constexpr int KV = 3; __VA_ARGS__; }     \
+    else { constexpr int KV = 4; __VA_ARGS__; }                     \
+  } while (0)
+
+// dropout(act(LN(x))) -> (y, mean, rstd), bitwise what
+// dropout_apply(ln_fwd(x, ...)[0], keep, seed) and ln_fwd return
+std::vector<at::Tensor> ln_act_drop_fwd(at::Tensor x, at::Tensor gamma,
+                                        at::Tensor beta, double eps,
+                                        int64_t act, double keep,
+                                        int64_t seed) {
+  check_f32(x, "x");
+  check_f32(gamma, "gamma");
+  check_f32(beta, "beta");
+  TORCH_CHECK(x.dim() == 2, "ln_act_drop_fwd: x must be [n, F]");
+  const int64_t n = x.size(0);
+  const int F = (int)x.size(1);
+  TORCH_CHECK(F <= 64 * LN_MAX_K, "ln_act_drop_fwd: F too large (", F, ")");
+  TORCH_CHECK(gamma.numel() == F && beta.numel() == F,
+              "ln_act_drop_fwd: gamma/beta must have F elements");
+  auto y = at::empty_like(x);
+  auto mean = at::empty({n}, x.options());
+  auto rstd = at::empty({n}, x.options());
+  if (n == 0 || F == 0) return {y, mean, rstd};
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const int blocks = (int)std::min<int64_t>((n + 3) / 4, 32768);
+  if (F % 4 == 0) {
+    LN_KV_DISPATCH(F, hipLaunchKernelGGL(
+        ln_act_drop_fwd_v4_kernel<KV>, dim3(blocks), dim3(256), 0, stream,
+        reinterpret_cast<const float4*>(x.data_ptr<float>()),
+        reinterpret_cast<const float4*>(gamma.data_ptr<float>()),
+        reinterpret_cast<const float4*>(beta.data_ptr<float>()),
+        reinterpret_cast<float4*>(y.data_ptr<float>()),
+        mean.data_ptr<float>(), rstd.data_ptr<float>(), n, F, (float)eps,
+        (int)act, (float)keep, (uint64_t)seed));
+    return {y, mean, rstd};
+  }
+  hipLaunchKernelGGL(ln_act_drop_fwd_kernel, dim3(blocks), dim3(256), 0,
+                     stream, x.data_ptr<float>(), gamma.data_ptr<float>(),
+                     beta.data_ptr<float>(), y.data_ptr<float>(),
+                     mean.data_ptr<float>(), rstd.data_ptr<float>(), n, F,
+                     (float)eps, (int)act, (float)keep, (uint64_t)seed);
+  return {y, mean, rstd};
+}
+
+// Backward of the above in one pass -> (dx, dgamma, dbeta, colsum(dx)).
+// dx is bitwise ln_bwd(x, dropout_apply(dy, keep, seed), ...)[0]; the three
+// column sums are taken in a fixed order (per-block partial rows, then
+// ln_colsum_finish_kernel), so repeated calls give identical bits.
+std::vector<at::Tensor> ln_act_drop_bwd(at::Tensor x, at::Tensor dy,
+                                        at::Tensor gamma, at::Tensor beta,
+                                        at::Tensor mean, at::Tensor rstd,
+                                        int64_t act, double keep,
+                                        int64_t seed) {
+  check_f32(x, "x");
+  check_f32(dy, "dy");
+  check_f32(gamma, "gamma");
+  check_f32(beta, "beta");
+  check_f32(mean, "mean");
+  check_f32(rstd, "rstd");
+  TORCH_CHECK(x.dim() == 2 && dy.sizes() == x.sizes(),
+              "ln_act_drop_bwd: x and dy must be [n, F]");
+  const int64_t n = x.size(0);
+  const int F = (int)x.size(1);
+  TORCH_CHECK(F <= 64 * LN_MAX_K, "ln_act_drop_bwd: F too large (", F, ")");
+  TORCH_CHECK(gamma.numel() == F && beta.numel() == F && mean.numel() == n &&
+                  rstd.numel() == n,
+              "ln_act_drop_bwd: gamma/beta [F] and mean/rstd [n] expected");
+  auto dx = at::empty_like(x);
+  if (n == 0 || F == 0) {
+    auto z = at::zeros({3, F}, x.options());
+    return {dx, z[0], z[1], z[2]};
+  }
+  auto dw = at::empty({3, F}, x.options());
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const int blocks = (int)std::min<int64_t>((n + 3) / 4, LN_FUSED_BLOCKS);
+  auto partial = at::empty({blocks, 3 * F}, x.options());
+  const size_t lds = 3 * (size_t)F * sizeof(float);
+  if (F % 4 == 0) {
+    LN_KV_DISPATCH(F, hipLaunchKernelGGL(
+        ln_act_drop_bwd_v4_kernel<KV>, dim3(blocks), dim3(256), lds, stream,
+        reinterpret_cast<const float4*>(x.data_ptr<float>()),
+        reinterpret_cast<const float4*>(dy.data_ptr<float>()),
+        reinterpret_cast<const float4*>(gamma.data_ptr<float>()),
+        reinterpret_cast<const float4*>(beta.data_ptr<float>()),
+        mean.data_ptr<float>(), rstd.data_ptr<float>(),
+        reinterpret_cast<float4*>(dx.data_ptr<float>()),
+        partial.data_ptr<float>(), n, F, (int)act, (float)keep,
+        (uint64_t)seed));
+  } else {
+    hipLaunchKernelGGL(ln_act_drop_bwd_kernel, dim3(blocks), dim3(256), lds,
+                       stream, x.data_ptr<float>(), dy.data_ptr<float>(),
+                       gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                       dx.data_ptr<float>(), partial.data_ptr<float>(), n, F,
+                       (int)act, (float)keep, (uint64_t)seed);
+  }
+  hipLaunchKernelGGL(ln_colsum_finish_kernel, dim3((3 * F + 15) / 16),
+                     dim3(256), 0, stream, partial.data_ptr<float>(),
+                     dw.data_ptr<float>(), blocks, 3 * F);
+  return {dx, dw[0], dw[1], dw[2]};
+}
+
 at::Tensor dropout_apply(at::Tensor x, double keep, int64_t seed) {
   check_f32(x, "x");
   auto out = at::empty_like(x);
@@ -2399,6 +2806,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ln_fwd", &ln_fwd, "row LayerNorm forward (y, mean, rstd); "
         "act=1 fuses ReLU");
   m.def("ln_bwd", &ln_bwd, "row LayerNorm backward (dx, dgamma, dbeta)");
+  m.def("ln_act_drop_fwd", &ln_act_drop_fwd,
+        "dropout(act(LayerNorm(x))) in one kernel (y, mean, rstd)");
+  m.def("ln_act_drop_bwd", &ln_act_drop_bwd,
+        "its backward in one pass (dx, dgamma, dbeta, colsum(dx))");
   m.def("dropout_apply", &dropout_apply,
         "mask-free dropout (splitmix64; same kernel fwd and bwd)");
   m.def("attn_project", &attn_project, "fused GAT el/er projections");
