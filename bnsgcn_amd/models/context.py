@@ -157,9 +157,15 @@ class GraphContext:
             n_src = self.n_rows if self.plan is None else self.plan.n_inner
             tip, tix, _ = transpose_csr(ip, ix, n_src)
             if self.indptr.is_cuda:
-                from ..ops.functional import _worklist_of
-                _worklist_of(ip)
-                _worklist_of(tip)
+                from ..ops import functional as BF
+                BF._worklist_of(ip)
+                BF._worklist_of(tip)
+                # static like the inner CSRs they are gathered from: the
+                # row-group form for the narrow calls of the projected
+                # output layer. The forward one is narrow-only unless
+                # BF.GROUP_FWD — a wide forward result feeds a ReLU mask.
+                BF.attach_rowgroups(ip, ix, n_src, wide=BF.GROUP_FWD)
+                BF.attach_rowgroups(tip, tix, ip.numel() - 1)
             self._rows_static = (ip, ix, tip, tix)
         return self._rows_static
 

@@ -131,6 +131,11 @@ class RowGroups(NamedTuple):
     ew: torch.Tensor        # uint8 [n_entries, R] edge count per row of group
     zero_rows: torch.Tensor  # int64 rows the kernel does not fully overwrite
     ratio: float            # n_entries / n_edges (1.0 for an edgeless CSR)
+    # which calls spmm_sum_raw may route to the format: the wide kernel
+    # (F / 4 > 32) and the narrow one (F / 4 <= 16) have keep rules of their
+    # own, and a forward CSR's format is narrow-only (functional.GROUP_FWD)
+    wide: bool = True
+    narrow: bool = False
 
 
 def build_rowgroups(indptr: torch.Tensor, indices: torch.Tensor, n_cols: int,

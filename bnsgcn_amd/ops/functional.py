@@ -38,6 +38,11 @@ import os as _os
 # without shared neighbours pays neither time nor memory.
 _GROUP = _os.environ.get("BNSGCN_SPMM_GROUP", "1") != "0"
 GROUP_TAU = float(_os.environ.get("BNSGCN_SPMM_GROUP_TAU", 0.6))
+# The same rule for narrow calls (F / 4 <= 16, spmm_sum_grouped_narrow_kernel),
+# measured on its own at F = 44 (profiles/BENCH_SUMMARY_narrowgroup.md): the
+# grouped kernel wins on both CSRs up to the largest ratio below 0.9 that
+# was measured, 0.66 (1.07x), and wins one CSR and ties the other at 0.92.
+GROUP_TAU_NARROW = float(_os.environ.get("BNSGCN_SPMM_GROUP_TAU_NARROW", 0.7))
 # GraphContext groups the TRANSPOSED inner CSR only (the backward SpMM).
 # transpose_csr leaves its rows in ascending column order, which is the
 # grouped kernel's summation order, and what the backward produces feeds
@@ -48,26 +53,48 @@ GROUP_TAU = float(_os.environ.get("BNSGCN_SPMM_GROUP_TAU", 0.6))
 # their largest element (profiles/BENCH_SUMMARY_rowgroup.md) — the size of
 # the per-row path's own run-to-run change when a hub row's atomics land
 # in another order, but on every run. BNSGCN_SPMM_GROUP_FWD=1 groups it too.
+# The train-row-gathered forward CSR of the output layer carries a format
+# for narrow calls only (its `wide` flag follows GROUP_FWD): a narrow
+# result is the logits and feeds no mask.
 GROUP_FWD = _os.environ.get("BNSGCN_SPMM_GROUP_FWD", "0") == "1"
 
 
-def attach_rowgroups(indptr, indices, n_cols):
-    """Build the row-group form of a STATIC CSR, apply the keep rule and
+def attach_rowgroups(indptr, indices, n_cols, wide=True, narrow=True):
+    """Build the row-group form of a STATIC CSR, apply the keep rules and
     cache the result on the indptr tensor (`_bns_rowgroups`, lifetime of
-    `_bns_worklist`). Returns the builder's entries/edges ratio, or None
-    when the path is off or the CSR is not on the GPU."""
+    `_bns_worklist`). `wide` / `narrow` name the calls the caller allows on
+    the format (F / 4 > 32, F / 4 <= 16); each is kept only below its own
+    threshold, and the format is cached if either is. Returns the builder's
+    entries/edges ratio, or None when the path is off or the CSR is not on
+    the GPU."""
     if not (_GROUP and indptr.is_cuda):
         return None
     from .csr_torch import build_rowgroups
     rg = build_rowgroups(indptr, indices, n_cols)
-    keep = rg.ratio <= GROUP_TAU
+    rg = rg._replace(wide=wide and rg.ratio <= GROUP_TAU,
+                     narrow=narrow and rg.ratio <= GROUP_TAU_NARROW)
+    keep = rg.wide or rg.narrow
     if keep:
         indptr._bns_rowgroups = rg
     if _os.environ.get("BNSGCN_SPMM_GROUP_LOG") == "1":
         print(f"rowgroup: R={rg.R} entries/edges {rg.ratio:.3f} "
-              f"({indices.numel()} edges) -> {'kept' if keep else 'dropped'}",
-              flush=True)
+              f"({indices.numel()} edges) -> "
+              f"{'kept' if keep else 'dropped'}"
+              f"{' wide' * rg.wide}{' narrow' * rg.narrow}", flush=True)
     return rg.ratio
+
+
+def _grouped_route(rg, x):
+    """True where spmm_sum_raw takes the row-group kernels: F % 4 == 0 and
+    either F / 4 > 32 on a format kept for wide calls, or F / 4 <= 16 with
+    an fp32 source on one kept for narrow calls (a bf16 source stays on
+    the per-row narrow kernel). Widths F / 4 = 17 .. 32 have no grouped
+    kernel."""
+    if rg is None or x.shape[1] % 4:
+        return False
+    f4 = x.shape[1] // 4
+    return (f4 > 32 and rg.wide) or (
+        0 < f4 <= 16 and rg.narrow and x.dtype == torch.float32)
 
 
 def round_bf16_raw(x):
@@ -90,7 +117,7 @@ def spmm_sum_raw(indptr, indices, x, src_scale=None, dst_scale=None, out=None):
     if use_hip(x):
         odt = torch.float32 if x.dtype == torch.bfloat16 else x.dtype
         rg = getattr(indptr, "_bns_rowgroups", None) if _GROUP else None
-        if rg is not None and x.shape[1] % 4 == 0 and x.shape[1] // 4 > 32:
+        if _grouped_route(rg, x):
             acc = out is not None
             if not acc:
                 out = torch.empty(indptr.numel() - 1, x.shape[1],

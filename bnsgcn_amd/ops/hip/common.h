@@ -6,6 +6,14 @@
 
 #define WAVE 64
 #define DEV_INLINE __device__ __forceinline__
+// Kernel attribute: code generation without the packed fp32 VALU forms
+// (v_pk_fma_f32 and kin), i.e. one v_fma_f32 per component. Same values;
+// new kernels are built this way.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define NO_PACKED_FP32
+#endif
 
 // ------------------------------------------------------------- work-list
 // View of the edge-balanced schedule built by

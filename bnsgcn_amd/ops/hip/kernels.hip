@@ -274,6 +274,139 @@ __global__ __launch_bounds__(256) void spmm_sum_narrow_kernel(
   }
 }
 
+// Row-group form of the narrow kernel (fp32 source, f4 <= G): the format
+// and schedule of spmm_sum_grouped_kernel, the lane mapping of
+// spmm_sum_narrow_kernel. Lane group g = lane / G takes ENTRY k + g of
+// the 64-entry chunk and lane j = lane % G float4 j of its source row,
+// read once; the lane then adds it to each of its R float4 accumulators
+// (one per row of the group) whose count is not 0. Lane groups hold
+// different entries, so that test is per lane: a select, not a branch —
+// and never 0 * val, which would carry an inf/NaN of the source row into
+// rows that have no edge to it. Four steps' reads are issued before the
+// first accumulate. At the end of the item the lane groups' accumulators
+// and their OR-ed weight words are combined with __shfl_xor over G, 2G,
+// ... and lane group 0 stores the rows the item holds an entry for.
+// Within a row, terms are added in a fixed order (per lane group in
+// ascending entry order, then the fixed combine), so a row of an unsplit
+// group is bit-reproducible from run to run.
+// Lane reads for that kernel, on the ds_bpermute builtin: the headers'
+// __shfl is not inlined into a kernel built with NO_PACKED_FP32.
+DEV_INLINE int lane_read(int v, int src_lane) {
+  return __builtin_amdgcn_ds_bpermute(src_lane << 2, v);
+}
+DEV_INLINE float lane_read(float v, int src_lane) {
+  return __int_as_float(lane_read(__float_as_int(v), src_lane));
+}
+
+template <bool ACC, int R, int G>
+__global__ __launch_bounds__(256) NO_PACKED_FP32
+void spmm_sum_grouped_narrow_kernel(
+    const int32_t* __restrict__ wgroup, const int64_t* __restrict__ wbeg,
+    const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
+    const int32_t* __restrict__ ecol, const uint32_t* __restrict__ ew,
+    const float* __restrict__ x, const float* __restrict__ src_scale,
+    const float* __restrict__ dst_scale, float* __restrict__ out, int f4,
+    int n_rows) {
+  constexpr int NW = R / 4;                  // 32-bit weight words per entry
+  constexpr int NG = WAVE / G;               // entries per step
+  constexpr int U = 4;                       // steps in flight
+  const WorkList wl = {wgroup, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<WAVE>(wl);
+  const int lane = wi.lane;
+  const int g = lane / G, j = lane % G;
+  const bool has = j < f4;
+  const int it_beg = __builtin_amdgcn_readfirstlane(wi.beg);
+  const int it_end = __builtin_amdgcn_readfirstlane(wi.end);
+  float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
+  const float4 zero4 = {0.f, 0.f, 0.f, 0.f};
+
+  for (int it = it_beg; it < it_end; ++it) {
+    const WorkItem wk = work_item(wl, it);   // wk.row = group id
+    float4 acc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = zero4;
+    uint32_t seen[NW];                       // OR of this lane group's words
+#pragma unroll
+    for (int q = 0; q < NW; ++q) seen[q] = 0u;
+
+    for (int64_t e0 = wk.beg; e0 < wk.end; e0 += WAVE) {
+      const int nv = (int)((wk.end - e0 < WAVE) ? (wk.end - e0) : WAVE);
+      int cid = 0;
+      float ssc = 1.0f;
+      // 0 past the chunk's end: a lane group without an entry adds nothing
+      uint32_t wv[NW];
+#pragma unroll
+      for (int q = 0; q < NW; ++q) wv[q] = 0u;
+      if (lane < nv) {
+        cid = ecol[e0 + lane];
+        if (src_scale) ssc = src_scale[cid];
+        load_group_w<NW>(ew + (e0 + lane) * NW, wv);
+      }
+      for (int k = 0; k < nv; k += U * NG) {
+        // k <= WAVE - U * NG, so every kk below is < WAVE
+        float4 val[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int kk = k + u * NG + g;
+          const int c = lane_read(cid, kk);
+          val[u] = (has && kk < nv) ? load_src4(x, (int64_t)c * f4 + j)
+                                    : zero4;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int kk = k + u * NG + g;
+          const float ss = src_scale ? lane_read(ssc, kk) : 1.0f;
+#pragma unroll
+          for (int q = 0; q < NW; ++q) {
+            const uint32_t w = (uint32_t)lane_read((int)wv[q], kk);
+            seen[q] |= w;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+              const float cnt = (float)((w >> (8 * b)) & 0xffu);
+              if (cnt != 0.f) {
+                // keeps the block under the lane mask: if-converted, each
+                // FMA would be followed by a select
+                asm volatile("");
+                const float s = cnt * ss;
+                float4& a = acc[4 * q + b];
+                a.x = fmaf(s, val[u].x, a.x);
+                a.y = fmaf(s, val[u].y, a.y);
+                a.z = fmaf(s, val[u].z, a.z);
+                a.w = fmaf(s, val[u].w, a.w);
+              }
+            }
+          }
+        }
+      }
+    }
+
+#pragma unroll
+    for (int off = G; off < WAVE; off <<= 1) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        acc[r].x += lane_read(acc[r].x, lane ^ off);
+        acc[r].y += lane_read(acc[r].y, lane ^ off);
+        acc[r].z += lane_read(acc[r].z, lane ^ off);
+        acc[r].w += lane_read(acc[r].w, lane ^ off);
+      }
+#pragma unroll
+      for (int q = 0; q < NW; ++q)
+        seen[q] |= (uint32_t)lane_read((int)seen[q], lane ^ off);
+    }
+    // a row is stored only if the item holds an entry for it
+    if (g == 0 && has) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int row = wk.row * R + r;
+        if (((seen[r / 4] >> (8 * (r % 4))) & 0xffu) != 0u && row < n_rows) {
+          const float ds = dst_scale ? dst_scale[row] : 1.0f;
+          store_row<ACC>(&out4[(int64_t)row * f4 + j], acc[r], wk.atomic, ds);
+        }
+      }
+    }
+  }
+}
+
 // float2 form for F % 2 == 0 (but % 4 != 0, e.g. the 602-wide Reddit
 // feature matrix: rows are 8-byte but not 16-byte aligned): 4 float2
 // accumulators cover 512 floats per edge walk — the scalar form needed
@@ -2036,7 +2169,8 @@ at::Tensor spmm_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
   return out;
 }
 
-// Row-group SpMM (spmm_sum_grouped_kernel): same contract as spmm_sum on
+// Row-group SpMM (spmm_sum_grouped_kernel at F / 4 > 32,
+// spmm_sum_grouped_narrow_kernel at F / 4 <= 16): same contract as spmm_sum on
 // the format of ops/csr_torch.build_rowgroups — (wgroup, wbeg, wend,
 // wave_start) schedule the entries (ecol, ew[n_entries, R]); `out` is
 // caller-allocated with the builder's zero_rows pre-zeroed unless acc.
@@ -2056,6 +2190,29 @@ void launch_grouped(const WorkListArgs& wl, bool acc, int f4,
   else
     launch(acc ? spmm_sum_grouped_kernel<T, true, R, 1>
                : spmm_sum_grouped_kernel<T, false, R, 1>);
+}
+
+// f4 <= 16, fp32 source: spmm_sum_grouped_narrow_kernel.
+void route_grouped_narrow(int R, const WorkListArgs& wl, bool acc, int f4,
+                          const at::Tensor& ecol, const at::Tensor& ew,
+                          const float* x, const float* ss, const float* ds,
+                          at::Tensor& out) {
+  auto launch = [&](auto kernel) {
+    launch_worklist(kernel, wl, 64, ecol.data_ptr<int32_t>(),
+                    reinterpret_cast<const uint32_t*>(ew.data_ptr<uint8_t>()),
+                    x, ss, ds, out.data_ptr<float>(), f4, (int)out.size(0));
+  };
+  switch (R) {
+    case 4:
+      launch(acc ? spmm_sum_grouped_narrow_kernel<true, 4, 16>
+                 : spmm_sum_grouped_narrow_kernel<false, 4, 16>);
+      break;
+    case 8:
+      launch(acc ? spmm_sum_grouped_narrow_kernel<true, 8, 16>
+                 : spmm_sum_grouped_narrow_kernel<false, 8, 16>);
+      break;
+    default: TORCH_CHECK(false, "spmm_sum_grouped: R must be 4 or 8, got ", R);
+  }
 }
 
 template <typename T>
@@ -2088,9 +2245,12 @@ at::Tensor spmm_sum_grouped(at::Tensor wgroup, at::Tensor wbeg,
               "ew: contiguous uint8 [n_entries, R] expected");
   const int R = (int)ew.size(1);
   const int F = x.size(1);
-  TORCH_CHECK(F % 4 == 0 && F / 4 > 32,
-              "spmm_sum_grouped covers F % 4 == 0 with F / 4 > 32, got F = ",
-              F);
+  const bool narrow = F / 4 <= 16;
+  TORCH_CHECK(F % 4 == 0 && (F / 4 > 32 || narrow),
+              "spmm_sum_grouped covers F % 4 == 0 with F / 4 > 32 or "
+              "F / 4 <= 16, got F = ", F);
+  TORCH_CHECK(!narrow || x.scalar_type() == at::kFloat,
+              "spmm_sum_grouped: F / 4 <= 16 takes an fp32 source");
   TORCH_CHECK(out.dim() == 2 && out.size(1) == F, "out: [n_rows, F] expected");
   if (src_scale.has_value())
     TORCH_CHECK(src_scale->numel() == x.size(0), "src_scale: one per x row");
@@ -2100,7 +2260,10 @@ at::Tensor spmm_sum_grouped(at::Tensor wgroup, at::Tensor wbeg,
   if (wgroup.numel() == 0 || wl.n_waves <= 0) return out;
   const float* ss = opt_ptr(src_scale);
   const float* ds = opt_ptr(dst_scale);
-  if (x.scalar_type() == at::kBFloat16)
+  if (narrow)
+    route_grouped_narrow(R, wl, acc, F / 4, ecol, ew, x.data_ptr<float>(),
+                         ss, ds, out);
+  else if (x.scalar_type() == at::kBFloat16)
     route_grouped(R, wl, acc, F / 4, ecol, ew, bf16_ptr(x), ss, ds, out);
   else
     route_grouped(R, wl, acc, F / 4, ecol, ew, x.data_ptr<float>(), ss, ds,

@@ -23,6 +23,13 @@ size and kernel time. --permute relabels the nodes with a random
 permutation first, which removes the id locality (the graph for finding
 the keep threshold GROUP_TAU).
 
+  python tools/spmm_micro.py --graph reddit --grouped --rows train \
+      --feats 44,48,64 --group-r 4,8 --gseg 256,512,1024,2048
+
+With narrow --feats (F <= 64) the same table compares the per-row narrow
+kernel with its row-group form, e.g. on the train-row-gathered CSRs the
+projected output layer runs on (the graphs for GROUP_TAU_NARROW).
+
   python tools/spmm_micro.py --graph reddit --feats 44,128,256 \
       --src-dtype fp32,bf16 [--grouped --group-r 4 --gseg 1024]
 
@@ -133,7 +140,8 @@ def grouped_table(label, ip, ix, n_src, F, a, src_dtype="fp32"):
             torch.cuda.synchronize()
             t_build = time.perf_counter() - t0
             ipg = ip.clone()
-            ipg._bns_rowgroups = rg
+            # narrow widths (F <= 64) run spmm_sum_grouped_narrow_kernel
+            ipg._bns_rowgroups = rg._replace(narrow=True)
             ts = [time_call(lambda: spmm_sum_raw(ipg, ix, x), a.iters)
                   for _ in range(a.repeats)]
             ref = spmm_sum_raw(ip, ix, x)
