@@ -97,6 +97,37 @@ def _grouped_route(rg, x):
         0 < f4 <= 16 and rg.narrow and x.dtype == torch.float32)
 
 
+# Source-row reads a wave of the wide kernels (F / 4 > 32:
+# spmm_sum_wide_kernel, spmm_sum_grouped_kernel) keeps in flight, per
+# kernel family and source type: the depth the sweep of
+# profiles/BENCH_SUMMARY_spmmdepth.md selected — 4 everywhere: with the
+# chunk and item prefetch in place deeper windows gain 0-3 % on one graph
+# and lose 1 % on another with an fp32 source, and a bf16 source gets
+# slower with depth. Every depth computes the same sums in the same
+# order. BNSGCN_SPMM_DEPTH forces one value for all four; a value the
+# kernels are not built for means 4. Unlike the other knobs it is read on
+# every spmm_sum_raw call, not once (tests set it per case), and it acts
+# here only: a direct call of the extension's spmm_sum / spmm_sum_grouped
+# gets the depth it passes, 4 by default.
+SPMM_DEPTHS = (4, 8, 16)
+SPMM_DEPTH_SWEPT = {("per_row", "fp32"): 4, ("per_row", "bf16"): 4,
+                    ("grouped", "fp32"): 4, ("grouped", "bf16"): 4}
+
+
+def spmm_depth(family, src_dtype):
+    """Depth passed to the extension for `family` in {"per_row", "grouped"}
+    and a source of torch dtype `src_dtype`."""
+    forced = _os.environ.get("BNSGCN_SPMM_DEPTH")
+    if forced is not None:
+        try:
+            depth = int(forced)
+        except ValueError:
+            depth = 4
+        return depth if depth in SPMM_DEPTHS else 4
+    name = "bf16" if src_dtype == torch.bfloat16 else "fp32"
+    return SPMM_DEPTH_SWEPT[(family, name)]
+
+
 def round_bf16_raw(x):
     """The source operand of --agg-dtype bf16: x rounded once to bf16,
     round to nearest even. On the GPU the HIP cast kernel returns a bf16
@@ -108,10 +139,13 @@ def round_bf16_raw(x):
     return x.float().bfloat16().to(x.dtype)
 
 
-def spmm_sum_raw(indptr, indices, x, src_scale=None, dst_scale=None, out=None):
+def spmm_sum_raw(indptr, indices, x, src_scale=None, dst_scale=None, out=None,
+                 depth=None):
     """x may be a bf16 source (round_bf16_raw); the result is fp32 then.
     The bf16 kernels cover F % 4 == 0: other widths upcast the rounded
-    copy and take the fp32 kernels — the same numbers, no byte saving."""
+    copy and take the fp32 kernels — the same numbers, no byte saving.
+    `depth` (4, 8 or 16) overrides spmm_depth for this call (tests,
+    tools/spmm_micro); None means routed."""
     if x.dtype == torch.bfloat16 and not (use_hip(x) and x.shape[1] % 4 == 0):
         x = x.float()
     if use_hip(x):
@@ -124,8 +158,9 @@ def spmm_sum_raw(indptr, indices, x, src_scale=None, dst_scale=None, out=None):
                                   dtype=odt, device=x.device)
                 if rg.zero_rows.numel():
                     out.index_fill_(0, rg.zero_rows, 0.0)
-            return get_ext().spmm_sum_grouped(*rg.sched, rg.ecol, rg.ew, x,
-                                              src_scale, dst_scale, out, acc)
+            return get_ext().spmm_sum_grouped(
+                *rg.sched, rg.ecol, rg.ew, x, src_scale, dst_scale, out, acc,
+                spmm_depth("grouped", x.dtype) if depth is None else depth)
         wrow, wbeg, wend, wave_start, zero_rows = _worklist_of(indptr)
         acc = out is not None
         if not acc:
@@ -136,7 +171,9 @@ def spmm_sum_raw(indptr, indices, x, src_scale=None, dst_scale=None, out=None):
             if zero_rows.numel():
                 out.index_fill_(0, zero_rows, 0.0)
         return get_ext().spmm_sum(wrow, wbeg, wend, wave_start, indices, x,
-                                  src_scale, dst_scale, out, acc)
+                                  src_scale, dst_scale, out, acc,
+                                  spmm_depth("per_row", x.dtype)
+                                  if depth is None else depth)
     return ref.spmm_sum(indptr, indices, x, src_scale, dst_scale, out)
 
 

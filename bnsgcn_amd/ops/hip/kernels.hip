@@ -22,13 +22,16 @@ namespace {
 // ops/csr_torch.build_worklist — heavy (power-law hub) rows are split
 // across items and combined with atomicAdd, so no wave serializes a
 // 100k+-edge row. Per 64-edge chunk the wave loads 64 column ids (and
-// src scales) with ONE coalesced load each and broadcasts them via
-// __shfl, so the row-feature loads are address-independent and the
-// unrolled inner loop keeps several 1-KiB row reads in flight (the naive
+// src scales) with ONE coalesced load each and broadcasts them (__shfl,
+// or readlane where the index is wave-uniform), so the row-feature loads
+// are address-independent and several row reads are in flight (the naive
 // row-loop form serializes two dependent loads per edge behind
 // s_waitcnt vmcnt(0) — measured 25x slower).
-// Feature dim is covered in passes of 2 float4 per lane (512 floats);
-// scalar variant (4 floats/lane/pass) handles F % 4 != 0.
+// Kernels by width: F % 4 == 0 and f4 = F / 4 <= 16 narrow (edge-parallel),
+// f4 <= 32 half-wave (spmm_sum_vec4_kernel, unrolled inner loop), wider
+// rows the depth-U gather stream (spmm_sum_wide_kernel; row-group form
+// spmm_sum_grouped_kernel), 1 or 2 float4 per lane and pass; F % 2 == 0
+// float2, otherwise scalar (4 floats/lane/pass).
 
 DEV_INLINE void f4_axpy(float4& a, float ss, const float4 v) {
   a.x += ss * v.x; a.y += ss * v.y; a.z += ss * v.z; a.w += ss * v.w;
@@ -43,9 +46,11 @@ __global__ __launch_bounds__(256) void spmm_sum_vec4_kernel(
     const int32_t* __restrict__ indices, const T* __restrict__ x,
     const float* __restrict__ src_scale, const float* __restrict__ dst_scale,
     float* __restrict__ out, int f4) {
-  // SUBW = scheduling width: 64 (full wave) for wide rows, 32 (half-wave
-  // subgroups, independent items per half) when f4 <= 32 so narrow
-  // feature dims (e.g. h=128 -> f4=32) keep every lane busy.
+  // SUBW = scheduling width: 32 (half-wave subgroups, independent items
+  // per half) for f4 <= 32, so narrow feature dims (e.g. h=128 -> f4=32)
+  // keep every lane busy. Only SUBW = 32 is instantiated: wider rows run
+  // spmm_sum_wide_kernel, so fB below is never live (the body is the
+  // former common one, kept as it was).
   // (A strided schedule — the waves of an XCD walking consecutive items
   // to share one sliding src window in L2 — was measured and LOSES ~1-6%:
   // drifting waves break their own temporal locality,
@@ -96,7 +101,7 @@ __global__ __launch_bounds__(256) void spmm_sum_vec4_kernel(
 // steers an entry is wave-uniform: the test `w != 0` is a scalar branch.
 // It is a correctness requirement, not an optimisation — a branch-free
 // 0 * v would carry an inf/NaN of the source row into rows that have no
-// edge to it. Four row reads are issued before the first accumulate.
+// edge to it. The kernel runs on the depth-U gather stream below.
 // Within a row, terms are added in ascending column order, so a row of an
 // unsplit group is bit-reproducible from run to run.
 template <int NW>
@@ -110,30 +115,151 @@ DEV_INLINE void load_group_w(const uint32_t* __restrict__ p, uint32_t (&w)[NW]) 
   }
 }
 
-template <typename T, bool ACC, int R, int NV>
-__global__ __launch_bounds__(256) void spmm_sum_grouped_kernel(
-    const int32_t* __restrict__ wgroup, const int64_t* __restrict__ wbeg,
-    const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
-    const int32_t* __restrict__ ecol, const uint32_t* __restrict__ ew,
-    const T* __restrict__ x, const float* __restrict__ src_scale,
-    const float* __restrict__ dst_scale, float* __restrict__ out, int f4,
-    int n_rows) {
-  constexpr int NW = R / 4;                  // 32-bit weight words per entry
-  constexpr int U = 4;                       // row reads in flight
-  const WorkList wl = {wgroup, wbeg, wend, wave_start};
+// ------------------------------------------------ depth-U gather stream
+// Shared schedule of the two wide kernels below (per-row full-wave and
+// row-group). A wave's time there follows the number of source-row reads
+// it keeps in flight, not their bytes (profiles/BENCH_SUMMARY_spmmdepth.md),
+// so a wave waits for memory once per U entries and for nothing else but
+// an item's store:
+//  * window of U: U row reads are issued before the first accumulate;
+//    entry k is accumulated and its registers take the read of entry
+//    k + U at once, and the wave waits once per window;
+//  * chunk c's src scales — the one dependent load — and the ids (and
+//    weight words) of chunk c + 1, into a second register set, are loaded
+//    right behind chunk c's first U row reads, so neither is waited for
+//    on its own;
+//  * the next item's (row, beg, end) and first chunk are fetched during
+//    the current item's last chunk.
+// Entries are accumulated in ascending order into one accumulator per
+// (row, float4) whatever U is: the sums and their order are those of the
+// U = 4 form.
+template <int NW>
+struct EntryChunk {
+  int cid, ssc;                  // column id, src scale (float bits)
+  uint32_t w[NW ? NW : 1];       // row-group weight words (NW = 0: none)
+};
+
+// Entries of [e0, end) in one chunk: at most 64, 0 for an empty range.
+// Wave-uniform, and pinned to a scalar register: every branch on it is a
+// scalar branch.
+DEV_INLINE int chunk_count(int64_t e0, int64_t end) {
+  const int64_t left = end - e0;
+  return __builtin_amdgcn_readfirstlane(
+      left < WAVE ? (left > 0 ? (int)left : 0) : WAVE);
+}
+
+// Lane l < nv: id (and weight words) of entry e0 + l; nothing else is read.
+template <int NW>
+DEV_INLINE EntryChunk<NW> load_entry_ids(const int32_t* __restrict__ col,
+                                         const uint32_t* __restrict__ ew,
+                                         int64_t e0, int nv, int lane) {
+  EntryChunk<NW> c;
+  c.cid = 0;
+  c.ssc = __float_as_int(1.0f);
+#pragma unroll
+  for (int j = 0; j < (NW ? NW : 1); ++j) c.w[j] = 0u;
+  if (lane < nv) {
+    c.cid = col[e0 + lane];
+    if constexpr (NW > 0) load_group_w<NW>(ew + (e0 + lane) * NW, c.w);
+  }
+  return c;
+}
+
+template <int NW>
+DEV_INLINE void load_entry_scale(EntryChunk<NW>& c, int nv,
+                                 const float* __restrict__ src_scale,
+                                 int lane) {
+  if (src_scale && lane < nv) c.ssc = __float_as_int(src_scale[c.cid]);
+}
+
+// Entries 0 .. nv - 1 of one chunk, in order: accumulate(k, val) gets the
+// NV float4 of entry k's source row. behind_first() runs once, after the
+// opening U reads have been issued.
+template <int U, int NV, typename T, typename Acc, typename Hook>
+DEV_INLINE void gather_chunk(const T* __restrict__ x, int cid, int nv, int f4,
+                             const int (&fi)[NV], Acc&& accumulate,
+                             Hook&& behind_first) {
+  float4 val[U][NV];
+  auto read = [&](int k, float4 (&v)[NV]) __attribute__((always_inline)) {
+    const int64_t base = (int64_t)__builtin_amdgcn_readlane(cid, k) * f4;
+#pragma unroll
+    for (int q = 0; q < NV; ++q) v[q] = load_src4(x, base + fi[q]);
+  };
+  // One unconditional use of cid ahead of the branches below: its load is
+  // then waited for here, once. Left to the first read inside a branch,
+  // the wait is repeated in each of them as "everything outstanding", and
+  // the U opening reads go out one latency apart.
+  asm volatile("" ::"s"(__builtin_amdgcn_readlane(cid, 0)));
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (u < nv) read(u, val[u]);
+  behind_first();
+  int k = 0;
+  for (; k + 2 * U <= nv; k += U) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      accumulate(k + u, val[u]);
+      read(k + u + U, val[u]);
+      // keeps each read next to its accumulate: without it all U reads
+      // sink below the last accumulate of the window
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  // Fewer than 2 U entries left, the first U of them already read. The
+  // rest is read only after those are accumulated: reads issued between
+  // conditional accumulates would each be waited for on their own. The
+  // explicit s_waitcnt vmcnt(0) (every outstanding read is one the next
+  // loop needs) is there for the same reason: placed by the compiler
+  // inside the first branch, it would not count for the paths around it.
+  __builtin_amdgcn_s_waitcnt(0x0f70);
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (k + u < nv) accumulate(k + u, val[u]);
+  k += U;
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (k + u < nv) read(k + u, val[u]);
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (k + u < nv) accumulate(k + u, val[u]);
+}
+
+// The calling wave's items, each in passes of NV * 64 float4: init()
+// clears the accumulators, accumulate(k, val, chunk) adds entry k of the
+// chunk, store(row, atomic, fi, has) writes the pass out (work_item's row
+// and split flag). A lane past the row's end reads the row's last float4
+// instead (in bounds, one unconditional load) and has[] tells store to
+// skip it.
+template <int U, int NV, int NW, typename T, typename Init, typename Acc,
+          typename Store>
+DEV_INLINE void stream_items(const WorkList& wl,
+                             const int32_t* __restrict__ col,
+                             const uint32_t* __restrict__ ew,
+                             const T* __restrict__ x,
+                             const float* __restrict__ src_scale, int f4,
+                             Init&& init, Acc&& accumulate, Store&& store) {
   const WaveItems wi = wave_items<WAVE>(wl);
   const int lane = wi.lane;
   const int it_beg = __builtin_amdgcn_readfirstlane(wi.beg);
   const int it_end = __builtin_amdgcn_readfirstlane(wi.end);
-  float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
-  const float4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  if (it_beg >= it_end) return;
 
+  // the item and the prefetched chunk are carried as plain scalars
+  int row = wl.row[it_beg];
+  int64_t beg = wl.beg[it_beg], end = wl.end[it_beg];
+  int nxt_nv = chunk_count(beg, end);
+  EntryChunk<NW> nxt = load_entry_ids<NW>(col, ew, beg, nxt_nv, lane);
   for (int it = it_beg; it < it_end; ++it) {
-    const WorkItem wk = work_item(wl, it);   // wk.row = group id
+    const bool has_next = it + 1 < it_end;
+    int n_row = 0;
+    int64_t n_beg = 0, n_end = 0;
+    if (has_next) {
+      n_row = wl.row[it + 1];
+      n_beg = wl.beg[it + 1];
+      n_end = wl.end[it + 1];
+    }
     for (int f0 = 0; f0 < f4; f0 += NV * WAVE) {
-      // a lane past the row's end reads the row's last float4 instead
-      // (in bounds, one unconditional 16-byte load — 8-byte for a bf16
-      // source) and never stores
+      const bool last_pass = f0 + NV * WAVE >= f4;
       int fi[NV];
       bool has[NV];
 #pragma unroll
@@ -142,22 +268,110 @@ __global__ __launch_bounds__(256) void spmm_sum_grouped_kernel(
         has[v] = fi[v] < f4;
         if (!has[v]) fi[v] = f4 - 1;
       }
-      float4 acc[NV][R];
-#pragma unroll
-      for (int v = 0; v < NV; ++v)
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[v][r] = zero4;
-      uint32_t seen[NW];                     // OR of the item's weight words
-#pragma unroll
-      for (int j = 0; j < NW; ++j) seen[j] = 0u;
+      if (f0 > 0) {                          // a further pass re-walks the item
+        nxt_nv = chunk_count(beg, end);
+        nxt = load_entry_ids<NW>(col, ew, beg, nxt_nv, lane);
+      }
+      init();
+      int64_t e0 = beg;
+      do {
+        EntryChunk<NW> cur = nxt;
+        const int cur_nv = nxt_nv;
+        const int64_t e1 = e0 + WAVE;
+        // nothing follows: nothing is read
+        const bool more = e1 < end;
+        const int64_t p0 = more ? e1 : n_beg;
+        nxt_nv = more ? chunk_count(e1, end)
+                      : (last_pass && has_next ? chunk_count(n_beg, n_end) : 0);
+        gather_chunk<U, NV>(
+            x, cur.cid, cur_nv, f4, fi,
+            [&](int k, const float4 (&val)[NV]) __attribute__((always_inline)) {
+              accumulate(k, val, cur);
+            },
+            // both queue up behind the chunk's first U row reads and
+            // are waited for together with them
+            [&]() __attribute__((always_inline)) {
+              load_entry_scale(cur, cur_nv, src_scale, lane);
+              nxt = load_entry_ids<NW>(col, ew, p0, nxt_nv, lane);
+            });
+        e0 = e1;
+      } while (e0 < end);
+      const bool atomic = row < 0;
+      store(atomic ? ~row : row, atomic, fi, has);
+    }
+    row = n_row; beg = n_beg; end = n_end;
+  }
+}
 
+// Per-row kernel for wide rows (f4 > 32) on the stream above: one float4
+// per lane for f4 <= 64 (NV = 1; h = 256), two beyond. T = source element
+// type as in spmm_sum_vec4_kernel, whose sums these are term for term.
+template <typename T, bool ACC, int NV, int U>
+__global__ __launch_bounds__(256) NO_PACKED_FP32
+void spmm_sum_wide_kernel(
+    const int32_t* __restrict__ wrow, const int64_t* __restrict__ wbeg,
+    const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
+    const int32_t* __restrict__ indices, const T* __restrict__ x,
+    const float* __restrict__ src_scale, const float* __restrict__ dst_scale,
+    float* __restrict__ out, int f4) {
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
+  float4 acc[NV];
+  stream_items<U, NV, 0>(
+      wl, indices, nullptr, x, src_scale, f4,
+      [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+      },
+      [&](int k, const float4 (&val)[NV], const EntryChunk<0>& ch)
+          __attribute__((always_inline)) {
+        const float ss = __int_as_float(__builtin_amdgcn_readlane(ch.ssc, k));
+#pragma unroll
+        for (int v = 0; v < NV; ++v) f4_axpy(acc[v], ss, val[v]);
+      },
+      [&](int row, bool atomic, const int (&fi)[NV], const bool (&has)[NV])
+          __attribute__((always_inline)) {
+        const float ds = dst_scale ? dst_scale[row] : 1.0f;
+        const int64_t ob = (int64_t)row * f4;
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+          if (has[v]) store_row<ACC>(&out4[ob + fi[v]], acc[v], atomic, ds);
+      });
+}
+
+template <typename T, bool ACC, int R, int NV, int U>
+__global__ __launch_bounds__(256) NO_PACKED_FP32
+void spmm_sum_grouped_kernel(
+    const int32_t* __restrict__ wgroup, const int64_t* __restrict__ wbeg,
+    const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
+    const int32_t* __restrict__ ecol, const uint32_t* __restrict__ ew,
+    const T* __restrict__ x, const float* __restrict__ src_scale,
+    const float* __restrict__ dst_scale, float* __restrict__ out, int f4,
+    int n_rows) {
+  constexpr int NW = R / 4;                  // 32-bit weight words per entry
+  const WorkList wl = {wgroup, wbeg, wend, wave_start};
+  float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
+  float4 acc[NV][R];
+  uint32_t seen[NW];                         // OR of the item's weight words
+  stream_items<U, NV, NW>(
+      wl, ecol, ew, x, src_scale, f4,
+      [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+          for (int r = 0; r < R; ++r)
+            acc[v][r] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int j = 0; j < NW; ++j) seen[j] = 0u;
+      },
       // one entry: add row `val` to every row of the group with w != 0
-      auto accumulate = [&](int k, const float4 (&val)[NV], int ssc,
-                            const uint32_t (&wv)[NW]) {
-        const float ss = __int_as_float(__builtin_amdgcn_readlane(ssc, k));
+      [&](int k, const float4 (&val)[NV], const EntryChunk<NW>& ch)
+          __attribute__((always_inline)) {
+        const float ss = __int_as_float(__builtin_amdgcn_readlane(ch.ssc, k));
 #pragma unroll
         for (int j = 0; j < NW; ++j) {
-          const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)wv[j], k);
+          const uint32_t w =
+              (uint32_t)__builtin_amdgcn_readlane((int)ch.w[j], k);
           seen[j] |= w;
 #pragma unroll
           for (int b = 0; b < 4; ++b) {
@@ -169,57 +383,23 @@ __global__ __launch_bounds__(256) void spmm_sum_grouped_kernel(
             }
           }
         }
-      };
-
-      for (int64_t e0 = wk.beg; e0 < wk.end; e0 += WAVE) {
-        const int nv = (int)((wk.end - e0 < WAVE) ? (wk.end - e0) : WAVE);
-        int cid = 0, ssc = __float_as_int(1.0f);
-        uint32_t wv[NW];
+      },
+      // a row is stored only if the item holds an entry for it
+      [&](int group, bool atomic, const int (&fi)[NV], const bool (&has)[NV])
+          __attribute__((always_inline)) {
 #pragma unroll
-        for (int j = 0; j < NW; ++j) wv[j] = 0u;
-        if (lane < nv) {
-          cid = ecol[e0 + lane];
-          if (src_scale) ssc = __float_as_int(src_scale[cid]);
-          load_group_w<NW>(ew + (e0 + lane) * NW, wv);
-        }
-        int k = 0;
-        for (; k + U <= nv; k += U) {
-          float4 val[U][NV];
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const int64_t base =
-                (int64_t)__builtin_amdgcn_readlane(cid, k + u) * f4;
+        for (int r = 0; r < R; ++r) {
+          const int row = group * R + r;
+          if (((seen[r / 4] >> (8 * (r % 4))) & 0xffu) != 0u && row < n_rows) {
+            const float ds = dst_scale ? dst_scale[row] : 1.0f;
+            const int64_t ob = (int64_t)row * f4;
 #pragma unroll
             for (int v = 0; v < NV; ++v)
-              val[u][v] = load_src4(x, base + fi[v]);
+              if (has[v])
+                store_row<ACC>(&out4[ob + fi[v]], acc[v][r], atomic, ds);
           }
-#pragma unroll
-          for (int u = 0; u < U; ++u) accumulate(k + u, val[u], ssc, wv);
         }
-        for (; k < nv; ++k) {
-          float4 val[NV];
-          const int64_t base = (int64_t)__builtin_amdgcn_readlane(cid, k) * f4;
-#pragma unroll
-          for (int v = 0; v < NV; ++v) val[v] = load_src4(x, base + fi[v]);
-          accumulate(k, val, ssc, wv);
-        }
-      }
-
-      // a row is stored only if the item holds an entry for it
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const int row = wk.row * R + r;
-        if (((seen[r / 4] >> (8 * (r % 4))) & 0xffu) != 0u && row < n_rows) {
-          const float ds = dst_scale ? dst_scale[row] : 1.0f;
-          const int64_t ob = (int64_t)row * f4;
-#pragma unroll
-          for (int v = 0; v < NV; ++v)
-            if (has[v])
-              store_row<ACC>(&out4[ob + fi[v]], acc[v][r], wk.atomic, ds);
-        }
-      }
-    }
-  }
+      });
 }
 
 // Narrow rows (f4 <= G float4, e.g. the 41->44-wide projected output
@@ -2108,10 +2288,33 @@ void launch_worklist(K kernel, const WorkListArgs& w, int subw,
 // Kernel routing of spmm_sum for one source type. A bf16 source has the
 // F % 4 == 0 kernels only: other widths are upcast by the caller
 // (ops/functional.spmm_sum_raw) and take the fp32 route.
+// Row reads a wave of the wide kernels keeps in flight (template parameter
+// U): 4, 8 or 16, anything else means 4. The caller chooses
+// (ops/functional.spmm_depth).
+int spmm_depth_of(int64_t depth) {
+  return depth == 8 || depth == 16 ? (int)depth : 4;
+}
+
+// spmm_sum_wide_kernel, f4 > 32: one float4 per lane up to f4 = 64.
+template <typename T, int U>
+void launch_wide(const WorkListArgs& wl, const int32_t* indices, const T* x,
+                 const float* ss, const float* ds, float* out, int f4,
+                 bool acc) {
+  auto launch = [&](auto kernel) {
+    launch_worklist(kernel, wl, 64, indices, x, ss, ds, out, f4);
+  };
+  if (f4 > 64)
+    launch(acc ? spmm_sum_wide_kernel<T, true, 2, U>
+               : spmm_sum_wide_kernel<T, false, 2, U>);
+  else
+    launch(acc ? spmm_sum_wide_kernel<T, true, 1, U>
+               : spmm_sum_wide_kernel<T, false, 1, U>);
+}
+
 template <typename T>
 void spmm_sum_route(const WorkListArgs& wl, const int32_t* indices,
                     const T* x, const float* ss, const float* ds, float* out,
-                    int F, bool acc) {
+                    int F, bool acc, int depth) {
   // f4 <= this runs the half-wave variant
   static const int subw32_max = env_int("BNSGCN_SPMM_SUBW32_MAX", 32);
   // f4 <= this runs the edge-parallel narrow kernel (0 disables it)
@@ -2127,8 +2330,11 @@ void spmm_sum_route(const WorkListArgs& wl, const int32_t* indices,
     launch(acc ? spmm_sum_vec4_kernel<T, true, 32>
                : spmm_sum_vec4_kernel<T, false, 32>, 32, F / 4);
   else if (F % 4 == 0)
-    launch(acc ? spmm_sum_vec4_kernel<T, true, 64>
-               : spmm_sum_vec4_kernel<T, false, 64>, 64, F / 4);
+    switch (depth) {
+      case 16: launch_wide<T, 16>(wl, indices, x, ss, ds, out, F / 4, acc); break;
+      case 8: launch_wide<T, 8>(wl, indices, x, ss, ds, out, F / 4, acc); break;
+      default: launch_wide<T, 4>(wl, indices, x, ss, ds, out, F / 4, acc);
+    }
   else if constexpr (std::is_same<T, float>::value) {
     if (F % 2 == 0)
       launch(acc ? spmm_sum_vec2_kernel<true> : spmm_sum_vec2_kernel<false>,
@@ -2146,7 +2352,7 @@ at::Tensor spmm_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
                     at::Tensor wave_start, at::Tensor indices, at::Tensor x,
                     c10::optional<at::Tensor> src_scale,
                     c10::optional<at::Tensor> dst_scale,
-                    at::Tensor out, bool acc) {
+                    at::Tensor out, bool acc, int64_t depth) {
   // `out` is always caller-allocated: accumulate when acc, otherwise the
   // kernel overwrites every non-empty row (caller pre-zeroed split/empty
   // rows — ops/csr_torch.build_worklist zero_rows). x is fp32 or bf16,
@@ -2161,11 +2367,11 @@ at::Tensor spmm_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
   if (x.scalar_type() == at::kBFloat16)
     spmm_sum_route(wl, indices.data_ptr<int32_t>(), bf16_ptr(x),
                    opt_ptr(src_scale), opt_ptr(dst_scale),
-                   out.data_ptr<float>(), F, acc);
+                   out.data_ptr<float>(), F, acc, spmm_depth_of(depth));
   else
     spmm_sum_route(wl, indices.data_ptr<int32_t>(), x.data_ptr<float>(),
                    opt_ptr(src_scale), opt_ptr(dst_scale),
-                   out.data_ptr<float>(), F, acc);
+                   out.data_ptr<float>(), F, acc, spmm_depth_of(depth));
   return out;
 }
 
@@ -2174,7 +2380,7 @@ at::Tensor spmm_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
 // the format of ops/csr_torch.build_rowgroups — (wgroup, wbeg, wend,
 // wave_start) schedule the entries (ecol, ew[n_entries, R]); `out` is
 // caller-allocated with the builder's zero_rows pre-zeroed unless acc.
-template <typename T, int R>
+template <typename T, int R, int U>
 void launch_grouped(const WorkListArgs& wl, bool acc, int f4,
                     const at::Tensor& ecol, const at::Tensor& ew,
                     const T* x, const float* ss, const float* ds,
@@ -2185,11 +2391,11 @@ void launch_grouped(const WorkListArgs& wl, bool acc, int f4,
                     x, ss, ds, out.data_ptr<float>(), f4, (int)out.size(0));
   };
   if (f4 > 64)                      // a second float4 per lane
-    launch(acc ? spmm_sum_grouped_kernel<T, true, R, 2>
-               : spmm_sum_grouped_kernel<T, false, R, 2>);
+    launch(acc ? spmm_sum_grouped_kernel<T, true, R, 2, U>
+               : spmm_sum_grouped_kernel<T, false, R, 2, U>);
   else
-    launch(acc ? spmm_sum_grouped_kernel<T, true, R, 1>
-               : spmm_sum_grouped_kernel<T, false, R, 1>);
+    launch(acc ? spmm_sum_grouped_kernel<T, true, R, 1, U>
+               : spmm_sum_grouped_kernel<T, false, R, 1, U>);
 }
 
 // f4 <= 16, fp32 source: spmm_sum_grouped_narrow_kernel.
@@ -2218,10 +2424,23 @@ void route_grouped_narrow(int R, const WorkListArgs& wl, bool acc, int f4,
 template <typename T>
 void route_grouped(int R, const WorkListArgs& wl, bool acc, int f4,
                    const at::Tensor& ecol, const at::Tensor& ew, const T* x,
-                   const float* ss, const float* ds, at::Tensor& out) {
+                   const float* ss, const float* ds, at::Tensor& out,
+                   int depth) {
   switch (R) {
-    case 4: launch_grouped<T, 4>(wl, acc, f4, ecol, ew, x, ss, ds, out); break;
-    case 8: launch_grouped<T, 8>(wl, acc, f4, ecol, ew, x, ss, ds, out); break;
+    case 4:
+      switch (depth) {
+        case 16:
+          launch_grouped<T, 4, 16>(wl, acc, f4, ecol, ew, x, ss, ds, out);
+          break;
+        case 8:
+          launch_grouped<T, 4, 8>(wl, acc, f4, ecol, ew, x, ss, ds, out);
+          break;
+        default:
+          launch_grouped<T, 4, 4>(wl, acc, f4, ecol, ew, x, ss, ds, out);
+      }
+      break;
+    // R = 8 holds twice the accumulators and was not swept over the depth
+    case 8: launch_grouped<T, 8, 4>(wl, acc, f4, ecol, ew, x, ss, ds, out); break;
     // R = 16 was built and measured: slower than the per-row kernel at
     // every gseg (profiles/BENCH_SUMMARY_rowgroup.md), so not instantiated
     default: TORCH_CHECK(false, "spmm_sum_grouped: R must be 4 or 8, got ", R);
@@ -2233,7 +2452,7 @@ at::Tensor spmm_sum_grouped(at::Tensor wgroup, at::Tensor wbeg,
                             at::Tensor ecol, at::Tensor ew, at::Tensor x,
                             c10::optional<at::Tensor> src_scale,
                             c10::optional<at::Tensor> dst_scale,
-                            at::Tensor out, bool acc) {
+                            at::Tensor out, bool acc, int64_t depth) {
   check_src(x, "x");
   check_f32(out, "out");
   const WorkListArgs wl = worklist_args(wgroup, wbeg, wend, wave_start);
@@ -2264,10 +2483,11 @@ at::Tensor spmm_sum_grouped(at::Tensor wgroup, at::Tensor wbeg,
     route_grouped_narrow(R, wl, acc, F / 4, ecol, ew, x.data_ptr<float>(),
                          ss, ds, out);
   else if (x.scalar_type() == at::kBFloat16)
-    route_grouped(R, wl, acc, F / 4, ecol, ew, bf16_ptr(x), ss, ds, out);
+    route_grouped(R, wl, acc, F / 4, ecol, ew, bf16_ptr(x), ss, ds, out,
+                  spmm_depth_of(depth));
   else
     route_grouped(R, wl, acc, F / 4, ecol, ew, x.data_ptr<float>(), ss, ds,
-                  out);
+                  out, spmm_depth_of(depth));
   return out;
 }
 
@@ -2936,9 +3156,19 @@ at::Tensor gemm_tn_drop(at::Tensor g, at::Tensor x, double keep,
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  m.def("spmm_sum", &spmm_sum, "CSR SpMM sum with fused src/dst scales");
+  // depth: row reads a wave of the wide kernels (F / 4 > 32) keeps in
+  // flight, 4, 8 or 16; anything else means 4
+  m.def("spmm_sum", &spmm_sum, "CSR SpMM sum with fused src/dst scales",
+        py::arg("wrow"), py::arg("wbeg"), py::arg("wend"),
+        py::arg("wave_start"), py::arg("indices"), py::arg("x"),
+        py::arg("src_scale"), py::arg("dst_scale"), py::arg("out"),
+        py::arg("acc"), py::arg("depth") = 4);
   m.def("spmm_sum_grouped", &spmm_sum_grouped,
-        "row-group CSR SpMM sum with fused src/dst scales");
+        "row-group CSR SpMM sum with fused src/dst scales",
+        py::arg("wgroup"), py::arg("wbeg"), py::arg("wend"),
+        py::arg("wave_start"), py::arg("ecol"), py::arg("ew"), py::arg("x"),
+        py::arg("src_scale"), py::arg("dst_scale"), py::arg("out"),
+        py::arg("acc"), py::arg("depth") = 4);
   m.def("pack_rows", &pack_rows, "gather rows + per-row scale");
   m.def("cast_bf16", &cast_bf16, "fp32 -> bf16 copy, round to nearest even");
   m.def("scatter_add_rows", &scatter_add_rows, "scatter-add rows + scale");

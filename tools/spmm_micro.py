@@ -38,6 +38,14 @@ copy round_bf16_raw makes for --agg-dtype bf16 (the cast is not in the
 timed window). Every line then carries TB/s of requested rows: row reads
 (edges, or entries for the grouped kernel) x F x bytes per element of the
 source actually read, over the time of a call.
+
+  python tools/spmm_micro.py --graph reddit --depth 4,8,16 \
+      --src-dtype fp32,bf16 [--grouped --group-r 4 --gseg 1024]
+
+--depth times the wide kernels (F > 128) once per listed depth, the number
+of source-row reads a wave keeps in flight, instead of the routed one
+(ops.functional.spmm_depth); every line then names its depth. All depths
+compute the same sums in the same order.
 """
 import argparse
 import os
@@ -120,16 +128,22 @@ def device_csrs(c, train, which):
                                           ip.numel() - 1)]
 
 
-def grouped_table(label, ip, ix, n_src, F, a, src_dtype="fp32"):
+def depths_of(a):
+    """[None] (routed) or the listed depths."""
+    return [int(d) for d in a.depth.split(",")] if a.depth else [None]
+
+
+def grouped_table(label, ip, ix, n_src, F, a, src_dtype="fp32", depth=None):
     """Per-row kernel against the row-group kernel on one CSR."""
     from bnsgcn_amd.ops.csr_torch import build_rowgroups
     e = ix.numel()
     x32 = torch.randn(n_src, F, device="cuda")
     x, nbytes = source_of(x32, src_dtype)
-    base = [time_call(lambda: spmm_sum_raw(ip, ix, x), a.iters)
+    base = [time_call(lambda: spmm_sum_raw(ip, ix, x, depth=depth), a.iters)
             for _ in range(a.repeats)]
     med, spread = float(np.median(base)), max(base) - min(base)
-    print(f"{label} F={F} src={src_dtype} {e} edges: per-row {med*1e3:.3f} ms "
+    print(f"{label} F={F} src={src_dtype} depth={depth or 'routed'} {e} edges: "
+          f"per-row {med*1e3:.3f} ms "
           f"(spread {spread*1e3:.3f} over {a.repeats} x {a.iters}), "
           f"{e * F * nbytes / med / 1e12:.2f} TB/s requested", flush=True)
     for R in (int(r) for r in a.group_r.split(",")):
@@ -142,10 +156,11 @@ def grouped_table(label, ip, ix, n_src, F, a, src_dtype="fp32"):
             ipg = ip.clone()
             # narrow widths (F <= 64) run spmm_sum_grouped_narrow_kernel
             ipg._bns_rowgroups = rg._replace(narrow=True)
-            ts = [time_call(lambda: spmm_sum_raw(ipg, ix, x), a.iters)
+            ts = [time_call(lambda: spmm_sum_raw(ipg, ix, x, depth=depth),
+                            a.iters)
                   for _ in range(a.repeats)]
-            ref = spmm_sum_raw(ip, ix, x)
-            got = spmm_sum_raw(ipg, ix, x)
+            ref = spmm_sum_raw(ip, ix, x, depth=depth)
+            got = spmm_sum_raw(ipg, ix, x, depth=depth)
             err = float((got - ref).abs().max() / ref.abs().max())
             mb = (rg.ecol.numel() * (4 + R)
                   + sum(t.numel() * t.element_size() for t in rg.sched)) / 1e6
@@ -176,6 +191,9 @@ def main():
     p.add_argument("--src-dtype", default="fp32",
                    help="comma-separated subset of fp32,bf16: element type "
                         "of the gathered source rows")
+    p.add_argument("--depth", default="",
+                   help="comma-separated subset of 4,8,16: row reads in "
+                        "flight in the wide kernels (default: routed)")
     p.add_argument("--permute", action="store_true",
                    help="relabel nodes randomly (no id locality)")
     a = p.parse_args()
@@ -193,19 +211,26 @@ def main():
             for F in (int(f) for f in a.feats.split(",")):
                 if a.grouped:
                     for sd in src_dtypes:
-                        grouped_table(label, ip, ix, n_src, F, a, sd)
+                        for depth in depths_of(a):
+                            grouped_table(label, ip, ix, n_src, F, a, sd,
+                                          depth)
                     continue
                 x32 = torch.randn(n_src, F, device="cuda")
                 for sd in src_dtypes:
                     x, nbytes = source_of(x32, sd)
-                    ts = [time_call(lambda: spmm_sum_raw(ip, ix, x), a.iters)
-                          for _ in range(a.repeats)]
-                    dt = float(np.median(ts))
-                    print(f"spmm {label} {e} edges F={F} src={sd}: "
-                          f"{dt*1e3:.3f} ms (spread "
-                          f"{(max(ts)-min(ts))*1e3:.3f} over {a.repeats} x "
-                          f"{a.iters}), {e * F * nbytes / dt / 1e12:.2f} TB/s "
-                          f"requested", flush=True)
+                    for depth in depths_of(a):
+                        ts = [time_call(lambda: spmm_sum_raw(ip, ix, x,
+                                                             depth=depth),
+                                        a.iters)
+                              for _ in range(a.repeats)]
+                        dt = float(np.median(ts))
+                        print(f"spmm {label} {e} edges F={F} src={sd} "
+                              f"depth={depth or 'routed'}: "
+                              f"{dt*1e3:.3f} ms (spread "
+                              f"{(max(ts)-min(ts))*1e3:.3f} over {a.repeats} "
+                              f"x {a.iters}), "
+                              f"{e * F * nbytes / dt / 1e12:.2f} TB/s "
+                              f"requested", flush=True)
                     del x
                 del x32
 
