@@ -56,6 +56,9 @@ class GraphContext:
         # operand of every aggregate() once to bf16, forward and backward;
         # None (fp32) leaves it alone. Same rule in train and eval.
         self.agg_dtype: torch.dtype | None = None
+        # --gat-dtype: the same switch for the gathered operand of the GAT
+        # aggregation (ops/functional._SpMMEdge); attention stays fp32.
+        self.gat_dtype: torch.dtype | None = None
         in_deg = in_deg.to(dev).float()
         out_deg = out_deg.to(dev).float()
         self.in_norm_inv = _inv_sqrt(in_deg)       # GCN dst scale

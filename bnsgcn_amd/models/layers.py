@@ -231,7 +231,8 @@ class GATLayer(nn.Module):
             logits = F.sddmm_add(el, er, ip, ix, tip, tix, eperm,
                                  slope=self.negative_slope)
             alpha = self.attn_drop(F.segment_softmax(logits, ip))
-            out = F.spmm_edge_sum(z, alpha, ip, ix, tip, tix, eperm)
+            out = F.spmm_edge_sum(z, alpha, ip, ix, tip, tix, eperm,
+                                  src_dtype=ctx.gat_dtype)
             return out + self.bias.view(1, H, D) if self.bias is not None else out
 
         if halo_feat is not None:                  # layer 0 under use_pp
@@ -264,7 +265,8 @@ class GATLayer(nn.Module):
         p_attn = self.attn_drop.p if self.training else 0.0
         ai, ah = F.segment_softmax2(li, lh, inner5[0], hip, p_drop=p_attn)
         out = F.spmm_edge_sum2(z_in, ai, z_h, ah, inner5,
-                               (hip, hix, hbip, hbix, heperm))
+                               (hip, hix, hbip, hbix, heperm),
+                               src_dtype=ctx.gat_dtype)
         if self.bias is not None:
             out = out + self.bias.view(1, H, D)
         return out

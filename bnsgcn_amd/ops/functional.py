@@ -177,15 +177,28 @@ def spmm_sum_raw(indptr, indices, x, src_scale=None, dst_scale=None, out=None,
     return ref.spmm_sum(indptr, indices, x, src_scale, dst_scale, out)
 
 
+def _gat_src(x):
+    """A bf16 source of the GAT kernels (round_bf16_raw of z or grad) as the
+    kernels take it. The bf16 kernels cover D % 4 == 0 on the GPU: any other
+    shape, or a CPU tensor, upcasts the rounded copy and takes the fp32
+    path — the same numbers, no byte saving (as spmm_sum_raw does)."""
+    if x.dtype == torch.bfloat16 and not (use_hip(x) and x.shape[2] % 4 == 0):
+        return x.float()
+    return x
+
+
 def spmm_edge_raw(indptr, indices, eweight, x, out=None, wperm=None):
     """wperm: optional edge permutation applied to eweight INSIDE the HIP
-    kernel (fuses the w[eperm] gather of the transposed backward pass)."""
+    kernel (fuses the w[eperm] gather of the transposed backward pass).
+    x may be a bf16 source (round_bf16_raw); the result is fp32 then."""
+    x = _gat_src(x)
     if use_hip(x):
         wrow, wbeg, wend, wstart, zero_rows = _worklist_of(indptr)
         acc = out is not None
         if not acc:
+            odt = torch.float32 if x.dtype == torch.bfloat16 else x.dtype
             out = torch.empty(indptr.numel() - 1, x.shape[1], x.shape[2],
-                              dtype=x.dtype, device=x.device)
+                              dtype=odt, device=x.device)
             if zero_rows.numel():
                 out.index_fill_(0, zero_rows, 0.0)
         return get_ext().spmm_edge_sum(wrow, wbeg, wend, wstart, indptr,
@@ -196,6 +209,9 @@ def spmm_edge_raw(indptr, indices, eweight, x, out=None, wperm=None):
 
 
 def sddmm_dot_raw(indptr, indices, a_dst, b_src):
+    """b_src (the streamed operand) may be a bf16 source; a_dst and the
+    result are fp32."""
+    b_src = _gat_src(b_src)
     if use_hip(a_dst):
         wl = _worklist_of(indptr)[:4]
         return get_ext().sddmm_dot(*wl, indptr, indices,
@@ -293,10 +309,20 @@ def spmm_sum(x, indptr, indices, indptr_t, indices_t,
 
 
 class _SpMMEdge(Function):
-    """y[r,h] = Σ_{e∈row r} w[e,h] * x[col_e,h,:]  (GAT aggregate, K4/K5)."""
+    """y[r,h] = Σ_{e∈row r} w[e,h] * x[col_e,h,:]  (GAT aggregate, K4/K5).
+
+    src_dtype=torch.bfloat16 (--gat-dtype bf16) rounds the gathered operand
+    once to bf16: x in forward, grad in the backward for x (straight-
+    through). The backward for w streams the SAVED bf16 x against the fp32
+    grad, so gw is the exact derivative of the rounded forward. Weights,
+    accumulation and every result stay fp32."""
 
     @staticmethod
-    def forward(ctx, x, w, indptr, indices, indptr_t, indices_t, eperm_t):
+    def forward(ctx, x, w, indptr, indices, indptr_t, indices_t, eperm_t,
+                src_dtype=None):
+        ctx.src_dtype = src_dtype
+        if src_dtype == torch.bfloat16:
+            x = round_bf16_raw(x)
         ctx.save_for_backward(x, w, indptr, indices, indptr_t, indices_t, eperm_t)
         return spmm_edge_raw(indptr, indices, w, x)
 
@@ -306,26 +332,34 @@ class _SpMMEdge(Function):
         grad = grad.contiguous()
         gx = gw = None
         if ctx.needs_input_grad[0]:
-            gx = spmm_edge_raw(indptr_t, indices_t, w, grad, wperm=eperm_t)
+            gsrc = round_bf16_raw(grad) \
+                if ctx.src_dtype == torch.bfloat16 else grad
+            gx = spmm_edge_raw(indptr_t, indices_t, w, gsrc, wperm=eperm_t)
         if ctx.needs_input_grad[1]:
             gw = sddmm_dot_raw(indptr, indices, grad, x)
-        return gx, gw, None, None, None, None, None
+        return gx, gw, None, None, None, None, None, None
 
 
-def spmm_edge_sum(x, w, indptr, indices, indptr_t, indices_t, eperm_t):
-    return _SpMMEdge.apply(x, w, indptr, indices, indptr_t, indices_t, eperm_t)
+def spmm_edge_sum(x, w, indptr, indices, indptr_t, indices_t, eperm_t,
+                  src_dtype=None):
+    return _SpMMEdge.apply(x, w, indptr, indices, indptr_t, indices_t, eperm_t,
+                           check_src_dtype(src_dtype))
 
 
 class _SpMMEdge2(Function):
     """Inner + halo GAT aggregation accumulated into ONE output buffer —
     removes the [N, H, D]-sized elementwise add between the two edge-set
     results (~5% of the Yelp GAT epoch in bare CUDAFunctor_add kernels,
-    profiles/topk_gat2_r02.txt)."""
+    profiles/topk_gat2_r02.txt). src_dtype as in _SpMMEdge; one rounded
+    copy of grad serves the inner and the halo backward."""
 
     @staticmethod
     def forward(ctx, x_in, w_in, x_h, w_h,
                 ip, ix, tip, tix, eperm_t,
-                hip_, hix_, hbip, hbix, heperm_t):
+                hip_, hix_, hbip, hbix, heperm_t, src_dtype=None):
+        ctx.src_dtype = src_dtype
+        if src_dtype == torch.bfloat16:
+            x_in, x_h = round_bf16_raw(x_in), round_bf16_raw(x_h)
         ctx.save_for_backward(x_in, w_in, x_h, w_h, ip, ix, tip, tix,
                               eperm_t, hip_, hix_, hbip, hbix, heperm_t)
         out = spmm_edge_raw(ip, ix, w_in, x_in)
@@ -338,21 +372,27 @@ class _SpMMEdge2(Function):
          hip_, hix_, hbip, hbix, heperm_t) = ctx.saved_tensors
         grad = grad.contiguous()
         gx_in = gw_in = gx_h = gw_h = None
+        gsrc = grad
+        if ctx.src_dtype == torch.bfloat16 and (ctx.needs_input_grad[0]
+                                                or ctx.needs_input_grad[2]):
+            gsrc = round_bf16_raw(grad)
         if ctx.needs_input_grad[0]:
-            gx_in = spmm_edge_raw(tip, tix, w_in, grad, wperm=eperm_t)
+            gx_in = spmm_edge_raw(tip, tix, w_in, gsrc, wperm=eperm_t)
         if ctx.needs_input_grad[1]:
             gw_in = sddmm_dot_raw(ip, ix, grad, x_in)
         if ctx.needs_input_grad[2]:
-            gx_h = spmm_edge_raw(hbip, hbix, w_h, grad, wperm=heperm_t)
+            gx_h = spmm_edge_raw(hbip, hbix, w_h, gsrc, wperm=heperm_t)
         if ctx.needs_input_grad[3]:
             gw_h = sddmm_dot_raw(hip_, hix_, grad, x_h)
-        return (gx_in, gw_in, gx_h, gw_h) + (None,) * 10
+        return (gx_in, gw_in, gx_h, gw_h) + (None,) * 11
 
 
-def spmm_edge_sum2(x_in, w_in, x_h, w_h, inner_csrs5, halo_csrs5):
+def spmm_edge_sum2(x_in, w_in, x_h, w_h, inner_csrs5, halo_csrs5,
+                   src_dtype=None):
     """inner_csrs5 = (ip, ix, tip, tix, eperm_t); halo_csrs5 likewise."""
     return _SpMMEdge2.apply(x_in, w_in, x_h, w_h,
-                            *inner_csrs5, *halo_csrs5)
+                            *inner_csrs5, *halo_csrs5,
+                            check_src_dtype(src_dtype))
 
 
 class _SDDMMAdd(Function):

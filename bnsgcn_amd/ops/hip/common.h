@@ -98,6 +98,42 @@ DEV_INLINE float4 load_src4(const bf16_t* __restrict__ x, int64_t i) {
                      __uint_as_float(p.y << 16),
                      __uint_as_float(p.y & 0xffff0000u));
 }
+// Row reads by the register type R they land in (the gather stream's
+// window is an array of R): float4 is load_src4 above, for either source
+// type. uint4 / uint2 are 8 / 4 bf16 kept PACKED — one 16-byte (8-byte)
+// load per lane, widened only where they are consumed (bf16_widen), so a
+// read in flight holds half the registers of its fp32 expansion. i counts
+// in units of R.
+template <typename R> struct RowLoad;
+template <> struct RowLoad<float4> {
+  template <typename T>
+  static DEV_INLINE float4 at(const T* __restrict__ x, int64_t i) {
+    return load_src4(x, i);
+  }
+};
+template <> struct RowLoad<uint4> {
+  static DEV_INLINE uint4 at(const bf16_t* __restrict__ x, int64_t i) {
+    return reinterpret_cast<const uint4*>(x)[i];
+  }
+};
+template <> struct RowLoad<uint2> {
+  static DEV_INLINE uint2 at(const bf16_t* __restrict__ x, int64_t i) {
+    return reinterpret_cast<const uint2*>(x)[i];
+  }
+};
+
+// Packed bf16 -> fp32, exact: element 2j is the low half of word j.
+DEV_INLINE void bf16_widen(const uint2 p, float (&f)[4]) {
+  f[0] = __uint_as_float(p.x << 16); f[1] = __uint_as_float(p.x & 0xffff0000u);
+  f[2] = __uint_as_float(p.y << 16); f[3] = __uint_as_float(p.y & 0xffff0000u);
+}
+DEV_INLINE void bf16_widen(const uint4 p, float (&f)[8]) {
+  f[0] = __uint_as_float(p.x << 16); f[1] = __uint_as_float(p.x & 0xffff0000u);
+  f[2] = __uint_as_float(p.y << 16); f[3] = __uint_as_float(p.y & 0xffff0000u);
+  f[4] = __uint_as_float(p.z << 16); f[5] = __uint_as_float(p.z & 0xffff0000u);
+  f[6] = __uint_as_float(p.w << 16); f[7] = __uint_as_float(p.w & 0xffff0000u);
+}
+
 DEV_INLINE float load_src1(const float* __restrict__ x, int64_t i) {
   return x[i];
 }

@@ -173,17 +173,19 @@ DEV_INLINE void load_entry_scale(EntryChunk<NW>& c, int nv,
 }
 
 // Entries 0 .. nv - 1 of one chunk, in order: accumulate(k, val) gets the
-// NV float4 of entry k's source row. behind_first() runs once, after the
-// opening U reads have been issued.
-template <int U, int NV, typename T, typename Acc, typename Hook>
+// NV registers of type R (common.h RowLoad: float4, or 8 / 4 packed bf16)
+// of entry k's source row, whose length is f4 in units of R.
+// behind_first() runs once, after the opening U reads have been issued.
+template <int U, int NV, typename R = float4, typename T, typename Acc,
+          typename Hook>
 DEV_INLINE void gather_chunk(const T* __restrict__ x, int cid, int nv, int f4,
                              const int (&fi)[NV], Acc&& accumulate,
                              Hook&& behind_first) {
-  float4 val[U][NV];
-  auto read = [&](int k, float4 (&v)[NV]) __attribute__((always_inline)) {
+  R val[U][NV];
+  auto read = [&](int k, R (&v)[NV]) __attribute__((always_inline)) {
     const int64_t base = (int64_t)__builtin_amdgcn_readlane(cid, k) * f4;
 #pragma unroll
-    for (int q = 0; q < NV; ++q) v[q] = load_src4(x, base + fi[q]);
+    for (int q = 0; q < NV; ++q) v[q] = RowLoad<R>::at(x, base + fi[q]);
   };
   // One unconditional use of cid ahead of the branches below: its load is
   // then waited for here, once. Left to the first read inside a branch,
@@ -1459,6 +1461,311 @@ __global__ __launch_bounds__(256) void sddmm_dot_fast_kernel(
           p += __shfl_xor(p, off, WAVE);
         if (active && (lane & (grp - 1)) == 0)
           out[(e0 + k) * H + h] = p;
+      }
+    }
+  }
+}
+
+// ================= GAT kernels with a bf16 source (--gat-dtype bf16) =====
+// x is the [N, H, D] operand rounded once by cast_bf16; weights, g,
+// accumulators and outputs are fp32. Lane mapping of its own: a row is
+// S = H * D / V "slots" of V consecutive bf16 of ONE head (V = 8: one
+// 16-byte load, D % 8 == 0; V = 4: 8 bytes, D % 4 == 0), and a lane owns
+// NS of them, slot lane and slot lane + 64. [H=4, D=128] is exactly one
+// 64-lane x 16-byte read per edge, and H * D = 1024 is walked once
+// (NS = 2) where the fp32 kernel walks the edge list twice. Both kernels
+// run on the depth-U gather stream above (gather_chunk with packed
+// registers), driven by stream_edge_items.
+template <int V> struct BfRow;
+template <> struct BfRow<8> { typedef uint4 type; };
+template <> struct BfRow<4> { typedef uint2 type; };
+
+// What lane l holds of edge e0 + l of a chunk: column id, the index of its
+// weights (wperm ? wperm[e] : e) and, for H <= 4, the H weights themselves.
+struct EdgeChunk {
+  int cid;
+  int64_t we;
+  float w[4];
+};
+
+template <bool WEIGHTS>
+DEV_INLINE EdgeChunk load_edge_ids(const int32_t* __restrict__ indices,
+                                   const int64_t* __restrict__ wperm,
+                                   int64_t e0, int nv, int lane) {
+  EdgeChunk c = {0, 0, {0.f, 0.f, 0.f, 0.f}};
+  if (lane < nv) {
+    c.cid = indices[e0 + lane];
+    if constexpr (WEIGHTS) c.we = wperm ? wperm[e0 + lane] : e0 + lane;
+  }
+  return c;
+}
+
+// The chunk's one dependent load (through wperm in the backward): one
+// float4 per lane when H == 4 and w is 16-byte aligned (w_vec4).
+DEV_INLINE void load_edge_w(EdgeChunk& c, int nv, const float* __restrict__ w,
+                            int H, bool w_vec4, int lane) {
+  if (H > 4 || lane >= nv) return;
+  if (w_vec4) {
+    const float4 t = *reinterpret_cast<const float4*>(w + c.we * 4);
+    c.w[0] = t.x; c.w[1] = t.y; c.w[2] = t.z; c.w[3] = t.w;
+  } else {
+#pragma unroll
+    for (int h = 0; h < 4; ++h)
+      if (h < H) c.w[h] = w[c.we * H + h];
+  }
+}
+
+// stream_items for the edge kernels: the calling wave's items, each in
+// passes of NS * 64 slots of a row of S slots of register type R, on the
+// same schedule — window of U row reads, the next chunk's ids (and this
+// chunk's weights, WEIGHTS) loaded behind the chunk's first U reads, the
+// next item fetched during the last chunk. init(row, si, has) starts a
+// pass, accumulate(k, val, chunk, e0) takes entry k (edge e0 + k),
+// store(row, atomic, si, has) ends it. A lane past the row's end reads the
+// row's last slot instead (in bounds) and has[] is false for it.
+template <int U, int NS, typename R, bool WEIGHTS, typename Init, typename Acc,
+          typename Store>
+DEV_INLINE void stream_edge_items(const WorkList& wl,
+                                  const int32_t* __restrict__ indices,
+                                  const float* __restrict__ w,
+                                  const int64_t* __restrict__ wperm,
+                                  const bf16_t* __restrict__ x, int H,
+                                  bool w_vec4, int S, Init&& init,
+                                  Acc&& accumulate, Store&& store) {
+  const WaveItems wi = wave_items<WAVE>(wl);
+  const int lane = wi.lane;
+  const int it_beg = __builtin_amdgcn_readfirstlane(wi.beg);
+  const int it_end = __builtin_amdgcn_readfirstlane(wi.end);
+  if (it_beg >= it_end) return;
+
+  int row = wl.row[it_beg];
+  int64_t beg = wl.beg[it_beg], end = wl.end[it_beg];
+  int nxt_nv = chunk_count(beg, end);
+  EdgeChunk nxt = load_edge_ids<WEIGHTS>(indices, wperm, beg, nxt_nv, lane);
+  for (int it = it_beg; it < it_end; ++it) {
+    const bool has_next = it + 1 < it_end;
+    int n_row = 0;
+    int64_t n_beg = 0, n_end = 0;
+    if (has_next) {
+      n_row = wl.row[it + 1];
+      n_beg = wl.beg[it + 1];
+      n_end = wl.end[it + 1];
+    }
+    const bool atomic = row < 0;
+    const int r = atomic ? ~row : row;
+    for (int s0 = 0; s0 < S; s0 += NS * WAVE) {
+      const bool last_pass = s0 + NS * WAVE >= S;
+      int si[NS];
+      bool has[NS];
+#pragma unroll
+      for (int j = 0; j < NS; ++j) {
+        si[j] = s0 + j * WAVE + lane;
+        has[j] = si[j] < S;
+        if (!has[j]) si[j] = S - 1;
+      }
+      if (s0 > 0) {                          // a further pass re-walks the item
+        nxt_nv = chunk_count(beg, end);
+        nxt = load_edge_ids<WEIGHTS>(indices, wperm, beg, nxt_nv, lane);
+      }
+      init(r, si, has);
+      int64_t e0 = beg;
+      do {
+        EdgeChunk cur = nxt;
+        const int cur_nv = nxt_nv;
+        const int64_t e1 = e0 + WAVE;
+        const bool more = e1 < end;
+        const int64_t p0 = more ? e1 : n_beg;
+        nxt_nv = more ? chunk_count(e1, end)
+                      : (last_pass && has_next ? chunk_count(n_beg, n_end) : 0);
+        gather_chunk<U, NS, R>(
+            x, cur.cid, cur_nv, S, si,
+            [&](int k, const R (&val)[NS]) __attribute__((always_inline)) {
+              accumulate(k, val, cur, e0);
+            },
+            [&]() __attribute__((always_inline)) {
+              if constexpr (WEIGHTS) load_edge_w(cur, cur_nv, w, H, w_vec4, lane);
+              nxt = load_edge_ids<WEIGHTS>(indices, wperm, p0, nxt_nv, lane);
+            });
+        e0 = e1;
+      } while (e0 < end);
+      store(r, atomic, si, has);
+    }
+    row = n_row; beg = n_beg; end = n_end;
+  }
+}
+
+DEV_INLINE float readlane_f(float v, int k) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
+}
+
+// out[r,h,:] (+)= sum_e w[e',h] * float(x[col_e,h,:]), e' = wperm ? wperm[e]
+// : e. The weights are off the per-edge dependent chain for H <= 4: they
+// arrive with the chunk (load_edge_w), and per edge the lane's head weight
+// is H wave-uniform readlanes and a per-lane select. H > 4 keeps one load
+// per edge and slot. DV = D / V slots per head.
+template <bool ACC, int V, int NS>
+__global__ __launch_bounds__(256) NO_PACKED_FP32
+void spmm_edge_bf16_kernel(
+    const int32_t* __restrict__ wrow, const int64_t* __restrict__ wbeg,
+    const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
+    const int32_t* __restrict__ indices, const float* __restrict__ w,
+    const int64_t* __restrict__ wperm, const bf16_t* __restrict__ x,
+    float* __restrict__ out, int H, int DV, int S, int w_vec4) {
+  typedef typename BfRow<V>::type R;
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  float acc[NS][V];
+  int hs[NS];                                // head of each of the lane's slots
+  stream_edge_items<4, NS, R, true>(
+      wl, indices, w, wperm, x, H, w_vec4 != 0, S,
+      [&](int, const int (&si)[NS], const bool (&)[NS])
+          __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+          hs[j] = si[j] / DV;
+#pragma unroll
+          for (int i = 0; i < V; ++i) acc[j][i] = 0.f;
+        }
+      },
+      [&](int k, const R (&val)[NS], const EdgeChunk& ch, int64_t)
+          __attribute__((always_inline)) {
+        float wj[NS];
+        if (H <= 4) {
+          const float w0 = readlane_f(ch.w[0], k), w1 = readlane_f(ch.w[1], k),
+                      w2 = readlane_f(ch.w[2], k), w3 = readlane_f(ch.w[3], k);
+#pragma unroll
+          for (int j = 0; j < NS; ++j)
+            wj[j] = hs[j] == 0 ? w0 : hs[j] == 1 ? w1 : hs[j] == 2 ? w2 : w3;
+        } else {
+          const int64_t we =
+              ((int64_t)__builtin_amdgcn_readlane((int)(ch.we >> 32), k) << 32) |
+              (uint32_t)__builtin_amdgcn_readlane((int)ch.we, k);
+#pragma unroll
+          for (int j = 0; j < NS; ++j) wj[j] = w[we * H + hs[j]];
+        }
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+          float f[V];
+          bf16_widen(val[j], f);
+#pragma unroll
+          for (int i = 0; i < V; ++i) acc[j][i] += wj[j] * f[i];
+        }
+      },
+      [&](int row, bool atomic, const int (&si)[NS], const bool (&has)[NS])
+          __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+          if (!has[j]) continue;
+          float4* o = reinterpret_cast<float4*>(out) +
+                      ((int64_t)row * S + si[j]) * (V / 4);
+#pragma unroll
+          for (int q = 0; q < V / 4; ++q)
+            store_row<ACC>(o + q,
+                           make_float4(acc[j][4 * q], acc[j][4 * q + 1],
+                                       acc[j][4 * q + 2], acc[j][4 * q + 3]),
+                           atomic);
+        }
+      });
+}
+
+// gw[e,h] = <g[row_e,h,:], float(x[col_e,h,:])>, fast form (D % 8 == 0,
+// grp = D / 8 a power of two <= 64, H * D <= 1024): the lane holds the
+// 8 * NS fp32 values of the fixed dst row g[row] that face its slots, an
+// edge costs NS 16-byte loads with U edges in flight, the partial dot is
+// reduced over the grp-lane head group and the group leader stores. Split
+// rows need no atomics: each (e, h) is written once.
+template <int NS>
+__global__ __launch_bounds__(256) NO_PACKED_FP32
+void sddmm_dot_bf16_fast_kernel(
+    const int32_t* __restrict__ wrow, const int64_t* __restrict__ wbeg,
+    const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
+    const int32_t* __restrict__ indices, const float* __restrict__ g,
+    const bf16_t* __restrict__ x, float* __restrict__ out, int H, int grp,
+    int S) {
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+  const bool leader = (threadIdx.x & (grp - 1)) == 0;
+  float rg[NS][8];
+  int hs[NS];
+  bool live[NS];
+  stream_edge_items<4, NS, uint4, false>(
+      wl, indices, nullptr, nullptr, x, H, false, S,
+      [&](int row, const int (&si)[NS], const bool (&has)[NS])
+          __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+          hs[j] = si[j] / grp;
+          live[j] = has[j] && leader;
+          const int64_t gi = ((int64_t)row * S + si[j]) * 2;
+          const float4 a = g4[gi], b = g4[gi + 1];
+          const float m = has[j] ? 1.f : 0.f;    // clamped lanes add nothing
+          rg[j][0] = m * a.x; rg[j][1] = m * a.y; rg[j][2] = m * a.z;
+          rg[j][3] = m * a.w; rg[j][4] = m * b.x; rg[j][5] = m * b.y;
+          rg[j][6] = m * b.z; rg[j][7] = m * b.w;
+        }
+      },
+      [&](int k, const uint4 (&val)[NS], const EdgeChunk&, int64_t e0)
+          __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+          float f[8];
+          bf16_widen(val[j], f);
+          float p = 0.f;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) p += rg[j][i] * f[i];
+          for (int off = grp >> 1; off > 0; off >>= 1)
+            p += __shfl_xor(p, off, WAVE);
+          if (live[j]) out[(e0 + k) * H + hs[j]] = p;
+        }
+      },
+      [&](int, bool, const int (&)[NS], const bool (&)[NS])
+          __attribute__((always_inline)) {});
+}
+
+// General form for a bf16 x (any H, D % 4 == 0): sddmm_dot_vec4_kernel's
+// 4 x 16-lane subgroup pipeline with V-element bf16 loads.
+template <int V>
+__global__ __launch_bounds__(256) NO_PACKED_FP32
+void sddmm_dot_bf16_vec_kernel(
+    const int32_t* __restrict__ wrow, const int64_t* __restrict__ wbeg,
+    const int64_t* __restrict__ wend, const int32_t* __restrict__ wave_start,
+    const int32_t* __restrict__ indices, const float* __restrict__ g,
+    const bf16_t* __restrict__ x, float* __restrict__ out, int H, int D,
+    int HD) {
+  typedef typename BfRow<V>::type R;
+  const WorkList wl = {wrow, wbeg, wend, wave_start};
+  const WaveItems wi = wave_items<WAVE>(wl);
+  const int lane = wi.lane;
+  const int sg = lane >> 4;            // 4 subgroups of 16 lanes
+  const int gl = lane & 15;
+  const int DV = D / V, S = HD / V;
+  const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+  for (int it = wi.beg; it < wi.end; ++it) {
+    const WorkItem wk = work_item(wl, it);
+    const int64_t grow = (int64_t)wk.row * S;
+    for (int64_t e0 = wk.beg; e0 < wk.end; e0 += WAVE) {
+      const Chunk ch = load_chunk<WAVE>(indices, nullptr, e0, wk.end, lane);
+      for (int k0 = 0; k0 < ch.nv; k0 += 4) {
+        const int k = k0 + sg;
+        const bool act = k < ch.nv;
+        const int c = __shfl(ch.cid, act ? k : 0, WAVE);
+        const int64_t crow = (int64_t)c * S;
+        for (int h = 0; h < H; ++h) {
+          float p = 0.f;
+          if (act)
+            for (int d = gl; d < DV; d += 16) {
+              float f[V];
+              bf16_widen(RowLoad<R>::at(x, crow + h * DV + d), f);
+#pragma unroll
+              for (int q = 0; q < V / 4; ++q) {
+                const float4 a = g4[(grow + h * DV + d) * (V / 4) + q];
+                p += a.x * f[4 * q] + a.y * f[4 * q + 1] +
+                     a.z * f[4 * q + 2] + a.w * f[4 * q + 3];
+              }
+            }
+#pragma unroll
+          for (int off = 8; off > 0; off >>= 1) p += __shfl_xor(p, off, WAVE);
+          if (act && gl == 0) out[(e0 + k) * H + h] = p;
+        }
       }
     }
   }
@@ -2916,23 +3223,81 @@ std::vector<at::Tensor> segment_softmax2_backward(at::Tensor ip1, at::Tensor a1,
   return {d1, d2};
 }
 
+// A bf16 x of the GAT kernels ([N, H, D], cast_bf16 of z or grad): V = 8
+// bf16 per lane and load where D % 8 == 0, else 4. D % 4 != 0 has no bf16
+// kernel — the caller upcasts (ops/functional._gat_src).
+int gat_bf16_v(const at::Tensor& x, const char* op) {
+  const int D = x.size(2);
+  TORCH_CHECK(D % 4 == 0, op, ": a bf16 source covers D % 4 == 0, got D = ", D);
+  const int V = D % 8 == 0 ? 8 : 4;
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % (2 * V) == 0, op,
+              ": bf16 source must be ", 2 * V, "-byte aligned");
+  return V;
+}
+
+inline void check_src3(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 3 &&
+                  (t.scalar_type() == at::kFloat ||
+                   t.scalar_type() == at::kBFloat16),
+              name, " must be a contiguous [N, H, D] fp32 or bf16 CUDA tensor");
+}
+
+template <int V>
+void launch_spmm_edge_bf16(const WorkListArgs& wl, bool acc, int NS,
+                           const int32_t* indices, const float* w,
+                           const int64_t* wperm, const bf16_t* x, float* out,
+                           int H, int D) {
+  const int S = H * D / V;
+  const int w_vec4 = H == 4 && reinterpret_cast<uintptr_t>(w) % 16 == 0;
+  auto launch = [&](auto kernel) {
+    launch_worklist(kernel, wl, 64, indices, w, wperm, x, out, H, D / V, S,
+                    w_vec4);
+  };
+  if (NS == 1)
+    launch(acc ? spmm_edge_bf16_kernel<true, V, 1>
+               : spmm_edge_bf16_kernel<false, V, 1>);
+  else
+    launch(acc ? spmm_edge_bf16_kernel<true, V, 2>
+               : spmm_edge_bf16_kernel<false, V, 2>);
+}
+
 at::Tensor spmm_edge_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
                          at::Tensor wstart, at::Tensor indptr,
                          at::Tensor indices, at::Tensor w,
                          c10::optional<at::Tensor> wperm, at::Tensor x,
                          at::Tensor out, bool acc) {
-  // out is caller-allocated (split/empty rows pre-zeroed — see spmm_sum)
-  check_f32(w, "w"); check_f32(x, "x"); check_f32(out, "out");
+  // out is caller-allocated (split/empty rows pre-zeroed — see spmm_sum).
+  // x fp32 or bf16, w and out fp32 either way.
+  check_f32(w, "w"); check_src3(x, "x"); check_f32(out, "out");
   const WorkListArgs wl = worklist_args(wrow, wbeg, wend, wstart);
   const int n_rows = indptr.numel() - 1;
   const int H = x.size(1), D = x.size(2);
+  TORCH_CHECK(out.dim() == 3 && out.size(0) == n_rows && out.size(1) == H &&
+                  out.size(2) == D && w.dim() == 2 && w.size(1) == H,
+              "spmm_edge_sum: out [n_rows, H, D] and w [E, H] expected");
   if (indices.numel() == 0 || n_rows == 0) return out;
+  const int64_t* pp = wperm.has_value() ? wperm->data_ptr<int64_t>() : nullptr;
+  if (x.scalar_type() == at::kBFloat16) {
+    const int V = gat_bf16_v(x, "spmm_edge_sum");
+    TORCH_CHECK(wl.n_waves > 0, "spmm_edge_sum: empty work list");
+    // one slot per lane up to 64 slots, two beyond (and further passes
+    // past 128)
+    const int NS = H * D / V <= WAVE ? 1 : 2;
+    if (V == 8)
+      launch_spmm_edge_bf16<8>(wl, acc, NS, indices.data_ptr<int32_t>(),
+                               w.data_ptr<float>(), pp, bf16_ptr(x),
+                               out.data_ptr<float>(), H, D);
+    else
+      launch_spmm_edge_bf16<4>(wl, acc, NS, indices.data_ptr<int32_t>(),
+                               w.data_ptr<float>(), pp, bf16_ptr(x),
+                               out.data_ptr<float>(), H, D);
+    return out;
+  }
   if (D % 4 == 0 && wl.n_waves > 0) {
     launch_worklist(acc ? spmm_edge_vec4_kernel<true>
                         : spmm_edge_vec4_kernel<false>,
                     wl, 64, indices.data_ptr<int32_t>(), w.data_ptr<float>(),
-                    wperm.has_value() ? wperm->data_ptr<int64_t>() : nullptr,
-                    x.data_ptr<float>(), out.data_ptr<float>(), H, D / 4,
+                    pp, x.data_ptr<float>(), out.data_ptr<float>(), H, D / 4,
                     H * D / 4);
     return out;
   }
@@ -2949,15 +3314,36 @@ at::Tensor spmm_edge_sum(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
 at::Tensor sddmm_dot(at::Tensor wrow, at::Tensor wbeg, at::Tensor wend,
                      at::Tensor wstart, at::Tensor indptr, at::Tensor indices,
                      at::Tensor g, at::Tensor x) {
-  check_f32(g, "g"); check_f32(x, "x");
+  // g (the dst-row operand) fp32; x (streamed per edge) fp32 or bf16
+  check_f32(g, "g"); check_src3(x, "x");
   const WorkListArgs wl = worklist_args(wrow, wbeg, wend, wstart);
   const int H = x.size(1), D = x.size(2);
   const int HD = H * D;
-  auto out = at::empty({indices.numel(), H}, x.options());
+  TORCH_CHECK(g.dim() == 3 && g.size(0) == indptr.numel() - 1 &&
+                  g.size(1) == H && g.size(2) == D,
+              "sddmm_dot: g [n_rows, H, D] expected");
+  auto out = at::empty({indices.numel(), H}, g.options());
   if (indices.numel() == 0 || wl.n_waves <= 0) return out;
   const int grp = D / 8;
-  const bool fast = HD <= 512 && D % 8 == 0 && grp > 0 &&
-                    (grp & (grp - 1)) == 0;
+  const bool shape_ok = D % 8 == 0 && grp > 0 && (grp & (grp - 1)) == 0;
+  if (x.scalar_type() == at::kBFloat16) {
+    const int V = gat_bf16_v(x, "sddmm_dot");
+    auto launch = [&](auto kernel, int a, int b) {
+      launch_worklist(kernel, wl, 64, indices.data_ptr<int32_t>(),
+                      g.data_ptr<float>(), bf16_ptr(x), out.data_ptr<float>(),
+                      H, a, b);
+    };
+    if (shape_ok && grp <= WAVE && HD <= 1024) {
+      if (HD / 8 <= WAVE) launch(sddmm_dot_bf16_fast_kernel<1>, grp, HD / 8);
+      else launch(sddmm_dot_bf16_fast_kernel<2>, grp, HD / 8);
+    } else if (V == 8) {
+      launch(sddmm_dot_bf16_vec_kernel<8>, D, HD);
+    } else {
+      launch(sddmm_dot_bf16_vec_kernel<4>, D, HD);
+    }
+    return out;
+  }
+  const bool fast = HD <= 512 && shape_ok;
   launch_worklist(fast ? sddmm_dot_fast_kernel
                        : D % 4 == 0 ? sddmm_dot_vec4_kernel
                                     : sddmm_dot_gen_kernel,

@@ -88,7 +88,30 @@ def create_parser() -> argparse.ArgumentParser:
                         "backward) and halves the bytes of every row read; "
                         "scales, products, sums and outputs stay fp32. "
                         "Default: $BNSGCN_AGG_DTYPE, else fp32")
+    p.add_argument("--gat-dtype", "--gat_dtype", choices=["fp32", "bf16"],
+                   default=os.environ.get("BNSGCN_GAT_DTYPE", "fp32"),
+                   help="dtype of the source rows the GAT aggregation "
+                        "gathers: bf16 rounds z (forward) and the output "
+                        "gradient (backward) once and reads 16-byte bf16 "
+                        "rows; attention, sums and outputs stay fp32. "
+                        "Default: $BNSGCN_GAT_DTYPE, else fp32")
     return p
+
+
+def gat_dtype_of(args):
+    """torch dtype of --gat-dtype for GraphContext.gat_dtype (None = fp32),
+    validated like agg_dtype_of: the flag covers the GAT aggregation only,
+    so asking for it with another model is an error, never a silent no-op."""
+    import torch
+    name = getattr(args, "gat_dtype", "fp32")
+    if name not in ("fp32", "bf16"):
+        raise ValueError(f"--gat-dtype must be fp32 or bf16, got {name!r}")
+    if name == "bf16" and getattr(args, "model", None) != "gat":
+        raise ValueError(
+            "--gat-dtype bf16 covers the GAT aggregation only; use "
+            "--agg-dtype for GCN/GraphSAGE. Use --gat-dtype fp32 (and unset "
+            "BNSGCN_GAT_DTYPE) with --model gcn/graphsage.")
+    return torch.bfloat16 if name == "bf16" else None
 
 
 def agg_dtype_of(args):

@@ -31,7 +31,7 @@ from ..models.models import create_model
 from ..ops.functional import pack_rows_raw, spmm_sum_raw
 from ..parallel import GradReducer, HaloPlan, all_to_all_rows, init_distributed
 from ..utils.timer import comm_timer
-from .config import agg_dtype_of, graph_name_of
+from .config import agg_dtype_of, gat_dtype_of, graph_name_of
 
 
 # --------------------------------------------------------------- offline
@@ -133,6 +133,7 @@ class RankState:
 
     def __init__(self, part: Partition, args, device):
         agg_dtype = agg_dtype_of(args)      # raises on gat + bf16
+        gat_dtype = gat_dtype_of(args)      # raises on gcn/graphsage + bf16
         self.device = torch.device(device)
         self.part = part
         self.args = args
@@ -153,6 +154,7 @@ class RankState:
         self.ctx = GraphContext.for_partition(part, self.plan, dev,
                                               need_eperm=(args.model == "gat"))
         self.ctx.agg_dtype = agg_dtype
+        self.ctx.gat_dtype = gat_dtype
         self.halo_feat0 = None     # GAT use_pp layer-0 full halo features
         self.n_train_global = int(part.meta["n_train"])
         self.part_train = int(part.train_mask.sum())
@@ -227,6 +229,7 @@ class EvalState:
         self.plan.set_epoch(0)
         self.ctx = GraphContext.for_partition(part, self.plan, device)
         self.ctx.agg_dtype = agg_dtype_of(args)
+        self.ctx.gat_dtype = gat_dtype_of(args)
 
 
 @torch.no_grad()
@@ -337,6 +340,7 @@ class Evaluator:
             torch.from_numpy(g.adj_in.indptr), torch.from_numpy(g.adj_in.indices),
             torch.from_numpy(g.in_deg), torch.from_numpy(g.out_deg), self.device)
         ctx.agg_dtype = agg_dtype_of(self.args)
+        ctx.gat_dtype = gat_dtype_of(self.args)
         feat = _feat_to_device(g.feat, self.device)
         label = torch.from_numpy(g.label).to(self.device)
         return ctx, feat, label, g
@@ -380,6 +384,7 @@ def run(args, rank: int | None = None, world_size: int | None = None) -> dict:
     # built while every rank still sits on cuda:0 is duplicate-device and
     # aborts the whole job (same guard as bench.py:88-96)
     agg_dtype_of(args)      # --agg-dtype bf16 with GAT: fail at start-up
+    gat_dtype_of(args)      # --gat-dtype bf16 without GAT: likewise
     pre_rank = int(os.environ.get("RANK", rank if rank is not None else 0))
     pre_world = int(os.environ.get("WORLD_SIZE",
                                    world_size if world_size is not None else 1))

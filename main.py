@@ -12,7 +12,7 @@ import os
 import torch.multiprocessing as mp
 
 from bnsgcn_amd.runtime.config import (agg_dtype_of, create_parser,
-                                       graph_name_of)
+                                       gat_dtype_of, graph_name_of)
 from bnsgcn_amd.runtime.trainer import prepare_partitions, run
 
 
@@ -28,6 +28,7 @@ def _worker(local_idx: int, start: int, world: int, args):
 def main():
     args = create_parser().parse_args()
     agg_dtype_of(args)      # --agg-dtype bf16 + --model gat: fail before work
+    gat_dtype_of(args)      # --gat-dtype bf16 without --model gat: likewise
     args.graph_name = graph_name_of(args)
     if args.node_rank == 0 and not args.skip_partition:
         prepare_partitions(args)
