@@ -192,7 +192,37 @@ class GraphContext:
         self._rows_halo = (st.epoch, out, None)
         return out
 
+    def _inner_pos(self, rows: torch.Tensor, n_inner: int) -> torch.Tensor:
+        """int32 map inner id -> position in `rows` (-1: not a listed row),
+        built once: the rows are the static, ascending train rows."""
+        c = getattr(self, "_inner_pos_cache", None)
+        if c is None or c[0] is not rows:
+            pos = torch.full((n_inner,), -1, dtype=torch.int32,
+                             device=rows.device)
+            pos[rows] = torch.arange(rows.numel(), dtype=torch.int32,
+                                     device=rows.device)
+            c = self._inner_pos_cache = (rows, pos)
+        return c[1]
+
     def _build_rows_halo(self, rows: torch.Tensor, st: EpochState):
+        from ..ops import csr_torch
+        if csr_torch.plan_hip(st.halo_fwd_indptr):
+            # device build (ops/hip/plan_build.hip), one read-back: the
+            # gather as a segmented copy, the transpose as the sampled
+            # backward CSR filtered to the listed columns (its rows are in
+            # ascending column order, like the sorted transpose's), and
+            # both work lists
+            from ..ops._ext import require_ext
+            n_inner = st.halo_fwd_indptr.numel() - 1
+            out = require_ext().rows_halo_build(
+                st.halo_fwd_indptr, st.halo_fwd_indices, rows.contiguous(),
+                st.halo_bwd_indptr, st.halo_bwd_indices,
+                self._inner_pos(rows, n_inner), csr_torch.FILTER_SEG,
+                csr_torch.SEG, csr_torch.MAX_WAVES)
+            hfip, hfix, hbip, hbix = out[:4]
+            hfip._bns_worklist = tuple(out[4:9])
+            hbip._bns_worklist = tuple(out[9:14])
+            return (hfip, hfix, hbip, hbix)
         from ..ops.csr_torch import gather_rows_csr
         hfip, hfix = gather_rows_csr(st.halo_fwd_indptr, st.halo_fwd_indices,
                                      rows)

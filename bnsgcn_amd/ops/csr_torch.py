@@ -262,3 +262,78 @@ def gather_rows_csr(indptr: torch.Tensor, indices: torch.Tensor,
     offset_in_row = pos - new_indptr[row_of_new_edge]
     src_edge = starts[row_of_new_edge] + offset_in_row
     return new_indptr, indices[src_edge]
+
+
+# ------------------------------------------------- device plan build (HIP)
+# The per-epoch sampled-halo CSRs and work lists are built by the kernels of
+# ops/hip/plan_build.hip instead of the torch calls above: bit-identical
+# outputs, one host synchronisation per build instead of about ten, and no
+# sort (docs/DESIGN.md, "Filter-compact transpose"). PLAN_HIP is the switch:
+# on when the extension is loaded, BNSGCN_PLAN_TORCH=1 turns it off, and with
+# it off every caller runs the torch code of this module unchanged. It is a
+# module attribute read at call time (not the environment), so a test can
+# flip it. CPU tensors always take the torch path.
+from ._ext import has_ext, require_ext
+
+PLAN_HIP = has_ext() and os.environ.get("BNSGCN_PLAN_TORCH") != "1"
+# Edges per segment of csr_filter_cols: a row longer than this is walked by
+# several waves. 1024 = 16 ballot steps of 64 edges per wave; a hub row of
+# 750k edges becomes 733 independent waves instead of one.
+FILTER_SEG = 1024
+
+
+def plan_hip(t: torch.Tensor) -> bool:
+    """True where the plan build for tensor `t` goes to the HIP kernels."""
+    return bool(PLAN_HIP) and t.is_cuda
+
+
+def build_segments(indptr: torch.Tensor, L: int = None
+                   ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Static segment table of a CSR for csr_filter_cols: a segment is a
+    non-empty row, or a slice of at most L edges of a longer one.
+
+    Returns int64 (seg_beg [S], seg_end [S], row_seg [n_rows + 1]): segment
+    s covers edges seg_beg[s] .. seg_end[s], and row r owns segments
+    row_seg[r] .. row_seg[r + 1] (none if it is empty); row_seg[-1] = S."""
+    L = L or FILTER_SEG
+    device = indptr.device
+    deg = indptr[1:] - indptr[:-1]
+    nseg = (deg + (L - 1)) // L
+    row_seg = torch.zeros(deg.numel() + 1, dtype=torch.int64, device=device)
+    torch.cumsum(nseg, 0, out=row_seg[1:])
+    rows = torch.repeat_interleave(
+        torch.arange(deg.numel(), device=device), nseg)
+    k = torch.arange(rows.numel(), device=device) - row_seg[rows]
+    seg_beg = (indptr[rows] + k * L).to(torch.int64)
+    seg_end = torch.minimum(seg_beg + L, indptr[rows + 1].to(torch.int64))
+    return seg_beg.contiguous(), seg_end.contiguous(), row_seg
+
+
+def csr_gather_rows(indptr: torch.Tensor, indices: torch.Tensor,
+                    rows: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """gather_rows_csr, by the HIP segmented copy where plan_hip(indptr)
+    (int64 indptr and rows, int32 indices)."""
+    if plan_hip(indptr):
+        return tuple(require_ext().csr_gather_rows(indptr, indices, rows))
+    return gather_rows_csr(indptr, indices, rows)
+
+
+def csr_filter_cols(indptr: torch.Tensor, indices: torch.Tensor,
+                    colmap: torch.Tensor, segs: tuple
+                    ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Order-preserving column filter of a device CSR (HIP only): edge e is
+    kept iff colmap[indices[e]] >= 0 and its new column is that value.
+    colmap is int32, segs = build_segments(indptr). Returns (new_indptr
+    int64, new_indices int32, kept int64), kept[k] = original edge id of new
+    edge k. With rows sorted by column and colmap increasing over the kept
+    columns this is the transpose of gather_rows_csr(transpose, kept
+    columns), which is how the callers use it."""
+    return tuple(require_ext().csr_filter_cols(indptr, indices, colmap,
+                                               *segs))
+
+
+def build_worklist_hip(indptr: torch.Tensor, seg: int = None,
+                       max_waves: int = None):
+    """build_worklist on the device: the same five tensors, bit for bit."""
+    return tuple(require_ext().build_worklist(indptr, seg or SEG,
+                                              max_waves or MAX_WAVES))

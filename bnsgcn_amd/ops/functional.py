@@ -19,11 +19,18 @@ from ._ext import get_ext, use_hip
 
 def _worklist_of(indptr):
     """Edge-balanced work list for the device SpMM (csr_torch.build_worklist),
-    cached on the indptr tensor itself (same lifetime as the CSR)."""
+    cached on the indptr tensor itself (same lifetime as the CSR). A
+    contiguous int64 indptr on the GPU gets it from the device builder
+    (csr_torch.build_worklist_hip, the same tensors) while csr_torch.PLAN_HIP
+    is on; SEG and MAX_WAVES are read at call time either way."""
     wl = getattr(indptr, "_bns_worklist", None)
     if wl is None:
-        from .csr_torch import build_worklist
-        wl = build_worklist(indptr)
+        from . import csr_torch
+        if (csr_torch.plan_hip(indptr) and indptr.dtype == torch.int64
+                and indptr.is_contiguous()):
+            wl = csr_torch.build_worklist_hip(indptr)
+        else:
+            wl = csr_torch.build_worklist(indptr)
         indptr._bns_worklist = wl
     return wl
 

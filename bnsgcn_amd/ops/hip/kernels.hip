@@ -13,6 +13,7 @@
 #include <type_traits>
 #include "common.h"
 #include "gemm_tiled.h"
+#include "plan_build.h"
 
 namespace {
 
@@ -3596,4 +3597,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused GAT projection backward");
   m.def("segment_sum_edges", &segment_sum_edges,
         "segment sum of (permuted) edge values by CSR row");
+  // per-epoch plan build: csr_gather_rows, csr_filter_cols, build_worklist
+  // and the two composite builders (plan_build.hip)
+  bns::bind_plan_build(m);
 }

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from ..graph.store import Partition
+from ..ops import csr_torch
 from ..ops.csr_torch import gather_rows_csr, transpose_csr
 from ..ops.philox import sample_boundary
 
@@ -107,6 +108,44 @@ class HaloPlan:
                        for j in range(self.n_parts)]
         self._state: EpochState | None = None
         self._static = self.rate >= 1.0 or self.rate <= 0.0
+        # static half of the device plan build (ops/hip/plan_build.hip)
+        self._hip: tuple | None = None
+        if csr_torch.plan_hip(self.halo_indptr):
+            self._hip_static()
+
+    def _hip_static(self) -> tuple:
+        """What the device build keeps for the whole job: the transposed
+        halo CSR (rows = inner dst, cols = halo row) with its edge map, its
+        segment table, the halo-row -> recv-row map `pos` (all -1 between
+        builds) and the event after which `pos` is free again. Built once,
+        with the torch code; shared with the full-halo plan."""
+        if self._hip is None:
+            tip, tix, teperm = transpose_csr(self.halo_indptr,
+                                             self.halo_indices, self.n_inner)
+            pos = torch.full((self.halo_indptr.numel() - 1,), -1,
+                             dtype=torch.int32, device=self.device)
+            self._hip = (tix.contiguous(), teperm.contiguous(),
+                         csr_torch.build_segments(tip), pos, [None])
+        return self._hip
+
+    def _build_csrs_hip(self, hsel: torch.Tensor) -> tuple:
+        """Sampled backward and forward halo CSRs, eperm_t and both work
+        lists from one extension call with one read-back: the backward CSR
+        is a segmented copy of the sampled rows, the forward one the static
+        transpose filtered to them (hsel is ascending, so no sort)."""
+        from ..ops._ext import require_ext
+        tix, teperm, segs, pos, free = self._hip_static()
+        cur = torch.cuda.current_stream(self.device)
+        if free[0] is not None:       # a build on another stream holds pos
+            cur.wait_event(free[0])
+        out = require_ext().halo_epoch_build(
+            self.halo_indptr, self.halo_indices, hsel, tix, teperm, *segs,
+            pos, csr_torch.SEG, csr_torch.MAX_WAVES)
+        free[0] = cur.record_event()
+        bwd_ip, bwd_ix, fwd_ip, fwd_ix, eperm_t = out[:5]
+        bwd_ip._bns_worklist = tuple(out[5:10])
+        fwd_ip._bns_worklist = tuple(out[10:15])
+        return bwd_ip, bwd_ix, fwd_ip, fwd_ix, eperm_t
 
     def _sample(self, n: int, s: int, epoch: int, src: int, dst: int) -> torch.Tensor:
         """Sorted s-subset of [0,n) — device-side Philox + torch stable sort
@@ -194,15 +233,22 @@ class HaloPlan:
         hsel = (torch.cat(hsel_parts) if hsel_parts
                 else torch.zeros(0, dtype=torch.long, device=dev))
 
-        bwd_ip, bwd_ix = gather_rows_csr(self.halo_indptr, self.halo_indices, hsel)
-        fwd_ip, fwd_ix, eperm_f = transpose_csr(bwd_ip, bwd_ix, self.n_inner)
-        # eperm_f[k] = bwd edge of fwd edge k; invert for bwd -> fwd
-        eperm_t = torch.empty_like(eperm_f)
-        eperm_t[eperm_f] = torch.arange(eperm_f.numel(), device=eperm_f.device)
-        if dev.type == "cuda":
-            from ..ops.functional import _worklist_of
-            _worklist_of(bwd_ip)
-            _worklist_of(fwd_ip)
+        if csr_torch.plan_hip(hsel):
+            bwd_ip, bwd_ix, fwd_ip, fwd_ix, eperm_t = \
+                self._build_csrs_hip(hsel)
+        else:
+            bwd_ip, bwd_ix = gather_rows_csr(self.halo_indptr,
+                                             self.halo_indices, hsel)
+            fwd_ip, fwd_ix, eperm_f = transpose_csr(bwd_ip, bwd_ix,
+                                                    self.n_inner)
+            # eperm_f[k] = bwd edge of fwd edge k; invert for bwd -> fwd
+            eperm_t = torch.empty_like(eperm_f)
+            eperm_t[eperm_f] = torch.arange(eperm_f.numel(),
+                                            device=eperm_f.device)
+            if dev.type == "cuda":
+                from ..ops.functional import _worklist_of
+                _worklist_of(bwd_ip)
+                _worklist_of(fwd_ip)
 
         st = EpochState(
             epoch=epoch,

@@ -17,9 +17,11 @@ setup(
         CUDAExtension(
             "bnsgcn_amd._C",
             sources=["bnsgcn_amd/ops/hip/kernels.hip",
-                     "bnsgcn_amd/ops/hip/gemm_tiled.hip"],
+                     "bnsgcn_amd/ops/hip/gemm_tiled.hip",
+                     "bnsgcn_amd/ops/hip/plan_build.hip"],
             depends=["bnsgcn_amd/ops/hip/common.h",
-                     "bnsgcn_amd/ops/hip/gemm_tiled.h"],
+                     "bnsgcn_amd/ops/hip/gemm_tiled.h",
+                     "bnsgcn_amd/ops/hip/plan_build.h"],
             extra_compile_args={"nvcc": ["-O3"], "cxx": ["-O3"]},
         )
     ],
