@@ -46,25 +46,35 @@ class GNNBase(nn.Module):
                 nm = self.norm[i]
                 if isinstance(nm, LayerNorm) and self.activation is TF.relu:
                     return nm(h, act=True)     # fused LN+ReLU (K7+K9)
+                if (isinstance(nm, SyncBatchNorm)
+                        and self.activation is TF.relu
+                        and F.bn_fuse_active(h, self.training)):
+                    return nm(h, act=True)     # fused BN+ReLU (bn_fused.hip)
                 h = nm(h)
             h = self.activation(h)
         return h
 
     def _fuses_post(self, i, h) -> bool:
-        """True if layer i's LayerNorm, ReLU and the dropout in front of
-        layer i+1 run as one kernel each way (_post_dropout) on layer i's
-        output, which lives where its input h lives."""
-        return (i < self.n_layers - 1 and self.use_norm
-                and isinstance(self.norm[i], LayerNorm)
-                and self.activation is TF.relu
-                and F.ln_fuse_active(h, self.norm[i].weight.numel(),
-                                     self.dropout.p, self.training))
+        """True if layer i's LayerNorm or SyncBatchNorm, ReLU and the
+        dropout in front of layer i+1 run fused (_post_dropout) on layer
+        i's output, which lives where its input h lives."""
+        if not (i < self.n_layers - 1 and self.use_norm
+                and self.activation is TF.relu):
+            return False
+        if isinstance(self.norm[i], SyncBatchNorm):
+            return self.dropout.p > 0.0 and F.bn_fuse_active(h, self.training)
+        return F.ln_fuse_active(h, self.norm[i].weight.numel(),
+                                self.dropout.p, self.training)
 
     def _post_dropout(self, i, h, biases):
         """dropout(_post(i, h)) where _fuses_post holds. The dropout seed
         is drawn here, after layer i and before anything of layer i+1, so
         the draws keep their order and every mask is the unfused one.
-        `biases`: the bias parameters layer i deferred to this op."""
+        `biases`: the bias parameters layer i deferred to this op
+        (LayerNorm only: in front of SyncBatchNorm a layer keeps its own
+        bias gradient)."""
+        if isinstance(self.norm[i], SyncBatchNorm):
+            return self.norm[i].forward_dropout(h, True, self.dropout.p)
         return self.norm[i].forward_dropout(h, True, self.dropout.p, biases)
 
 
@@ -104,7 +114,8 @@ class GCN(GNNBase):
             dropped = self._fuses_post(i, h)
             # on the fused path the conv layer's GEMM biases get their
             # gradient from the LayerNorm backward (layers._gemm_bias)
-            biases = [] if (dropped and conv) else None
+            biases = [] if (dropped and conv and
+                            isinstance(self.norm[i], LayerNorm)) else None
             if conv:
                 h = lay(ctx, h, rows=rows, defer_bias=biases)
             else:

@@ -84,7 +84,19 @@ class SyncBatchNorm(nn.Module):
         self.weight = nn.Parameter(torch.ones(num_features))
         self.bias = nn.Parameter(torch.zeros(num_features))
 
-    def forward(self, x):
+    def forward(self, x, act: bool = False):
+        """act=True fuses the following ReLU: one HIP kernel sequence on the
+        GPU in training (ops/hip/bn_fused.hip), this path + relu elsewhere."""
+        if act:
+            return self.forward_dropout(x, True, 0.0)
         return _SyncBNFunc.apply(x, self.weight, self.bias, self.whole_size,
                                  self.running_mean, self.running_var,
                                  self.training, self.momentum, self.eps)
+
+    def forward_dropout(self, x, act: bool, p: float):
+        """dropout(self(x, act), p) of a training step on the fused kernels;
+        see F.sync_batch_norm_act_dropout."""
+        from ..ops import functional as F
+        return F.sync_batch_norm_act_dropout(
+            x, self.weight, self.bias, self.running_mean, self.running_var,
+            self.momentum, self.eps, act, p, self.training)

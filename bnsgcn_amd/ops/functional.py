@@ -726,6 +726,80 @@ def layer_norm_act_dropout(x, weight, bias, eps: float = 1e-5,
     return dropout(layer_norm(x, weight, bias, eps, act), p, training)
 
 
+# Fused SyncBatchNorm + ReLU + dropout for --norm batch (ops/hip/
+# bn_fused.hip, docs/DESIGN.md §5b): 3 passes over the activation forward
+# and 5 backward. BNSGCN_BN_FUSE=0 (or setting _BN_FUSE False) keeps
+# models/sync_bn._SyncBNFunc followed by relu and dropout(): the same
+# masks, about 13 and 18 passes.
+_BN_FUSE = _os.environ.get("BNSGCN_BN_FUSE", "1") != "0"
+
+
+def bn_fuse_active(x, training: bool) -> bool:
+    """True where sync_batch_norm_act_dropout runs the fused kernels on x:
+    HIP, fp32, 2-D, training."""
+    return (_BN_FUSE and training and x.dim() == 2
+            and x.dtype == torch.float32 and use_hip(x))
+
+
+class _SyncBNActDropoutF(Function):
+    """y = dropout(relu?(SyncBN(x))) over the bn_* kernels. The two
+    all-reduces ([Σx, Σx², rows] forward, [Σg, Σg·x̂] backward) stay here,
+    between the column-sum finish and the kernel that consumes the reduced
+    vector; a rank without rows contributes zeros to both. Saved: x and the
+    per-column mean, rstd, weight, bias — no x_hat, no mask — plus the
+    one-element global row count, which stays on the device."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum,
+                eps, act, keep, seed):
+        from ..models.sync_bn import _maybe_all_reduce
+        e = get_ext()
+        x = x.contiguous()
+        stats = e.bn_colsums_fwd(x)
+        _maybe_all_reduce(stats)
+        mean, rstd = e.bn_finalize(stats, running_mean, running_var,
+                                   momentum, eps)
+        w, b = weight.detach().contiguous(), bias.detach().contiguous()
+        ctx.save_for_backward(x, mean, rstd, w, b)
+        ctx.count = stats[-1:]
+        ctx.act, ctx.keep, ctx.seed = int(act), keep, seed
+        return e.bn_act_drop_fwd(x, mean, rstd, w, b, ctx.act, keep, seed)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from ..models.sync_bn import _maybe_all_reduce
+        e = get_ext()
+        x, mean, rstd, w, b = ctx.saved_tensors
+        dy = dy.contiguous()
+        tail = (ctx.act, ctx.keep, ctx.seed)
+        red = e.bn_colsums_bwd(x, dy, mean, rstd, w, b, ctx.count, *tail)
+        nf = x.shape[1]
+        _maybe_all_reduce(red[:2 * nf])
+        dx = e.bn_act_drop_bwd_dx(x, dy, mean, rstd, w, b, red, *tail)
+        return (dx, red[nf:2 * nf], red[:nf]) + (None,) * 7
+
+
+def sync_batch_norm_act_dropout(x, weight, bias, running_mean, running_var,
+                                momentum: float, eps: float,
+                                act: bool = False, p: float = 0.0,
+                                training: bool = False):
+    """dropout(relu?(SyncBatchNorm(x)), p, training). Fused where
+    bn_fuse_active(x, training) holds; the dropout seed is drawn exactly as
+    dropout() draws it and only when p > 0, so the RNG order and the masks
+    are those of the unfused path, which is taken everywhere else."""
+    if bn_fuse_active(x, training):
+        seed = int(torch.randint(0, 2**62, (1,)).item()) if p > 0.0 else 0
+        return _SyncBNActDropoutF.apply(x, weight, bias, running_mean,
+                                        running_var, momentum, eps, act,
+                                        1.0 - p, seed)
+    from ..models.sync_bn import _SyncBNFunc
+    y = _SyncBNFunc.apply(x, weight, bias, None, running_mean, running_var,
+                          training, momentum, eps)
+    if act:
+        y = torch.relu(y)
+    return dropout(y, p, training)
+
+
 def segment_softmax2_raw(indptr1, logits1, indptr2, logits2):
     if use_hip(logits1):
         return get_ext().segment_softmax2(indptr1, logits1, indptr2, logits2,

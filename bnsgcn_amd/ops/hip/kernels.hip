@@ -14,6 +14,7 @@
 #include "common.h"
 #include "gemm_tiled.h"
 #include "plan_build.h"
+#include "bn_fused.h"
 
 namespace {
 
@@ -3600,4 +3601,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // per-epoch plan build: csr_gather_rows, csr_filter_cols, build_worklist
   // and the two composite builders (plan_build.hip)
   bns::bind_plan_build(m);
+  // fused SyncBatchNorm + ReLU + dropout (bn_fused.hip)
+  bns::bind_bn_fused(m);
 }

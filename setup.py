@@ -18,10 +18,12 @@ setup(
             "bnsgcn_amd._C",
             sources=["bnsgcn_amd/ops/hip/kernels.hip",
                      "bnsgcn_amd/ops/hip/gemm_tiled.hip",
-                     "bnsgcn_amd/ops/hip/plan_build.hip"],
+                     "bnsgcn_amd/ops/hip/plan_build.hip",
+                     "bnsgcn_amd/ops/hip/bn_fused.hip"],
             depends=["bnsgcn_amd/ops/hip/common.h",
                      "bnsgcn_amd/ops/hip/gemm_tiled.h",
-                     "bnsgcn_amd/ops/hip/plan_build.h"],
+                     "bnsgcn_amd/ops/hip/plan_build.h",
+                     "bnsgcn_amd/ops/hip/bn_fused.h"],
             extra_compile_args={"nvcc": ["-O3"], "cxx": ["-O3"]},
         )
     ],
