@@ -15,6 +15,7 @@
 #include "gemm_tiled.h"
 #include "plan_build.h"
 #include "bn_fused.h"
+#include "bns_select.h"
 
 namespace {
 
@@ -3603,4 +3604,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   bns::bind_plan_build(m);
   // fused SyncBatchNorm + ReLU + dropout (bn_fused.hip)
   bns::bind_bn_fused(m);
+  // per-epoch boundary-node selection, all segments in one launch
+  // (bns_select.hip)
+  bns::bind_bns_select(m);
 }

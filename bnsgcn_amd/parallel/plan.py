@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from ..graph.store import Partition
-from ..ops import csr_torch
+from ..ops import bns_select, csr_torch
 from ..ops.csr_torch import gather_rows_csr, transpose_csr
 from ..ops.philox import sample_boundary
 
@@ -112,6 +112,10 @@ class HaloPlan:
         self._hip: tuple | None = None
         if csr_torch.plan_hip(self.halo_indptr):
             self._hip_static()
+        # static half of the device sampler (ops/hip/bns_select.hip)
+        self._sel: tuple | None = None
+        if bns_select.sample_hip(dev, self.n_out + self.n_in):
+            self._select_hip()
 
     def _hip_static(self) -> tuple:
         """What the device build keeps for the whole job: the transposed
@@ -146,6 +150,34 @@ class HaloPlan:
         bwd_ip._bns_worklist = tuple(out[5:10])
         fwd_ip._bns_worklist = tuple(out[10:15])
         return bwd_ip, bwd_ix, fwd_ip, fwd_ix, eperm_t
+
+    def _select_hip(self) -> tuple:
+        """What the device sampler (ops/hip/bns_select.hip) keeps for the
+        whole job: the selection over every (peer, direction) segment in
+        the peer-major order of `_build`, and `pack_scale`, which does not
+        depend on the epoch (its consumers only read it). Keyed by the
+        sizes: the full-halo plan (GraphContext.full_state) is a copy of
+        this object with other ones."""
+        key = (tuple(self.send_size), tuple(self.recv_size), self.unit_ratio)
+        if self._sel is None or self._sel[0] != key:
+            me, segs, scale, bnd_off = self.rank, [], [], 0
+            for j in range(self.n_parts):
+                s, n = self.send_size[j], self.n_out[j]
+                if j != me and s > 0:
+                    segs.append((n, s, me, j, bns_select.KIND_PACK, bnd_off))
+                    scale.append(torch.full((s,), n / s, dtype=torch.float32,
+                                            device=self.device))
+                bnd_off += n
+                r, m = self.recv_size[j], self.n_in[j]
+                if j != me and r > 0:
+                    segs.append((m, r, j, me, bns_select.KIND_HALO,
+                                 self.halo_start[j]))
+            sel = bns_select.PlanSelect(
+                segs, self.seed, self.device, torch.cat(self.boundary),
+                self.halo_out_norm_inv_full, self.halo_in_deg_full)
+            self._sel = (key, sel, torch.cat(scale) if scale
+                         and not self.unit_ratio else None)
+        return self._sel[1:]
 
     def _sample(self, n: int, s: int, epoch: int, src: int, dst: int) -> torch.Tensor:
         """Sorted s-subset of [0,n) — device-side Philox + torch stable sort
@@ -204,7 +236,9 @@ class HaloPlan:
         self._state = st
         return st
 
-    def _build(self, epoch: int) -> EpochState:
+    def _sample_torch(self, epoch: int) -> tuple:
+        """(pack_idx, pack_scale, hsel) of one epoch, one `_sample` per
+        peer and direction, peer-major."""
         dev = self.device
         me = self.rank
         pack_parts, scale_parts, hsel_parts = [], [], []
@@ -232,6 +266,19 @@ class HaloPlan:
             pack_scale = None
         hsel = (torch.cat(hsel_parts) if hsel_parts
                 else torch.zeros(0, dtype=torch.long, device=dev))
+        return pack_idx, pack_scale, hsel
+
+    def _build(self, epoch: int) -> EpochState:
+        dev = self.device
+        me = self.rank
+        if bns_select.sample_hip(dev, self.n_out + self.n_in):
+            # every segment in one launch, final values (bns_select.hip)
+            sel, pack_scale = self._select_hip()
+            pack_idx, hsel, out_norm_inv, in_deg = sel(epoch)
+        else:
+            pack_idx, pack_scale, hsel = self._sample_torch(epoch)
+            out_norm_inv = self.halo_out_norm_inv_full[hsel]
+            in_deg = self.halo_in_deg_full[hsel]
 
         if csr_torch.plan_hip(hsel):
             bwd_ip, bwd_ix, fwd_ip, fwd_ix, eperm_t = \
@@ -257,8 +304,7 @@ class HaloPlan:
             halo_fwd_indptr=fwd_ip, halo_fwd_indices=fwd_ix,
             halo_bwd_indptr=bwd_ip, halo_bwd_indices=bwd_ix,
             halo_eperm_t=eperm_t,
-            halo_out_norm_inv=self.halo_out_norm_inv_full[hsel],
-            halo_in_deg=self.halo_in_deg_full[hsel],
+            halo_out_norm_inv=out_norm_inv, halo_in_deg=in_deg,
         )
         st.send_counts[me] = 0
         st.recv_counts[me] = 0

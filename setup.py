@@ -19,11 +19,13 @@ setup(
             sources=["bnsgcn_amd/ops/hip/kernels.hip",
                      "bnsgcn_amd/ops/hip/gemm_tiled.hip",
                      "bnsgcn_amd/ops/hip/plan_build.hip",
-                     "bnsgcn_amd/ops/hip/bn_fused.hip"],
+                     "bnsgcn_amd/ops/hip/bn_fused.hip",
+                     "bnsgcn_amd/ops/hip/bns_select.hip"],
             depends=["bnsgcn_amd/ops/hip/common.h",
                      "bnsgcn_amd/ops/hip/gemm_tiled.h",
                      "bnsgcn_amd/ops/hip/plan_build.h",
-                     "bnsgcn_amd/ops/hip/bn_fused.h"],
+                     "bnsgcn_amd/ops/hip/bn_fused.h",
+                     "bnsgcn_amd/ops/hip/bns_select.h"],
             extra_compile_args={"nvcc": ["-O3"], "cxx": ["-O3"]},
         )
     ],

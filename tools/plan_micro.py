@@ -1,15 +1,20 @@
-"""Per-epoch plan build on one rank of a real multi-partition job: the torch
-path (csr_torch.PLAN_HIP off) against the device build
-(ops/hip/plan_build.hip), same process, same inputs, alternating.
+"""Per-epoch plan build on one rank of a real multi-partition job, three
+variants in the same process on the same inputs, alternating:
+
+  torch    torch sampling and torch CSR surgery (csr_torch.PLAN_HIP and
+           bns_select.SAMPLE_HIP off);
+  hip      the device CSR build (ops/hip/plan_build.hip) with torch
+           sampling: Philox keys, argsort, sort and index per peer and
+           direction;
+  hip+sel  the device CSR build with the one-launch device sampling
+           (ops/hip/bns_select.hip) — the default path.
 
   python tools/plan_micro.py --store /tmp/plan_micro_store
 
 The graph is partitioned on the CPU with the project's partitioner (reused
 if the store exists), one rank is loaded and HaloPlan._build(epoch) plus
 GraphContext._build_rows_halo(train rows) is timed over --builds
-consecutive epochs per round. Both variants include the boundary sampling
-itself (Philox keys, argsort and sort per peer), which this switch does
-not change. Reported per build:
+consecutive epochs per round. Reported per build:
 
   host ms   host clock from the first call to the return of the last one,
             no device synchronise added: what the launching thread loses,
@@ -86,9 +91,10 @@ def main():
     assert torch.cuda.is_available(), "plan_micro measures on a GPU"
 
     from bnsgcn_amd.models.context import GraphContext
-    from bnsgcn_amd.ops import csr_torch
+    from bnsgcn_amd.ops import bns_select, csr_torch
     from bnsgcn_amd.parallel.plan import HaloPlan
     assert csr_torch.PLAN_HIP, "extension not loaded or BNSGCN_PLAN_TORCH=1"
+    assert bns_select.SAMPLE_HIP, "BNSGCN_SAMPLE_TORCH=1"
     dev = "cuda:0"
     part = load_partition(a.store, args.graph_name, a.rank)
     plan = HaloPlan(part, a.rate, seed=0, device=dev)
@@ -107,16 +113,21 @@ def main():
           f"{st.hsel.numel()}, sampled edges {st.halo_bwd_indices.numel()}, "
           f"train rows {rows.numel()}", flush=True)
 
-    variants = (("torch", False), ("hip", True))
-    for _, on in variants:                      # warm both paths
-        csr_torch.PLAN_HIP = on
+    variants = (("torch", (False, False)), ("hip", (True, False)),
+                ("hip+sel", (True, True)))
+
+    def switch(on):
+        csr_torch.PLAN_HIP, bns_select.SAMPLE_HIP = on
+
+    for _, on in variants:                      # warm every path
+        switch(on)
         for e in range(3):
             build(e)
     torch.cuda.synchronize()
     res = {name: {"host": [], "gpu": []} for name, _ in variants}
     for rnd in range(a.rounds):
         for name, on in variants:
-            csr_torch.PLAN_HIP = on
+            switch(on)
             e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
             torch.cuda.synchronize()
             e0.record()
@@ -129,17 +140,17 @@ def main():
             gpu = e0.elapsed_time(e1) / a.builds
             res[name]["host"].append(host)
             res[name]["gpu"].append(gpu)
-            print(f"round {rnd} {name:5s} host {host:8.3f} ms/build  "
+            print(f"round {rnd} {name:7s} host {host:8.3f} ms/build  "
                   f"gpu {gpu:8.3f} ms/build", flush=True)
     for name, on in variants:
-        csr_torch.PLAN_HIP = on
+        switch(on)
         try:
             k, s = count_calls(build, 999)
             calls = f"kernels {k} syncs {s}"
         except Exception as exc:                # profiler unavailable
             calls = f"launch counts not measured ({type(exc).__name__})"
         h, g = res[name]["host"], res[name]["gpu"]
-        print(f"{name:5s} host min-max {min(h):.3f}-{max(h):.3f} ms  "
+        print(f"{name:7s} host min-max {min(h):.3f}-{max(h):.3f} ms  "
               f"gpu min-max {min(g):.3f}-{max(g):.3f} ms  {calls}",
               flush=True)
 
