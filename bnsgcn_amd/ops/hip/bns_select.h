@@ -5,7 +5,8 @@
 
 namespace bns {
 
-// Adds bns_select_philox, bns_select_raw and BNS_SELECT_CAP to the module.
+// Adds bns_select_philox, bns_select_raw, BNS_SELECT_CAP and
+// BNS_SELECT_SLICE_MIN to the module.
 void bind_bns_select(pybind11::module& m);
 
 }  // namespace bns

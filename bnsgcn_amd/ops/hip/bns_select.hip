@@ -36,6 +36,10 @@
 // dependency. LDS: 8 KB histogram + 12 B per candidate = 56 KB + for
 // CAP = 4096.
 //
+// One workgroup is serial in n: the caller gives large segments to the
+// sliced form (bns_select_sliced.hip) in the same call, through a second
+// table; the device code both share is in bns_select_dev.h.
+//
 // Preconditions (checked by ops/bns_select.py, which builds the table, not
 // on the device): n < 2^31; the outputs hold out_off + min(s, n) elements;
 // base + n is within boundary_cat / the per-row arrays; raw keys lie in
@@ -48,91 +52,15 @@
 #include <vector>
 #include "common.h"
 #include "bns_select.h"
+#include "bns_select_dev.h"
 
 namespace {
 
+using namespace bns;
+
 constexpr int TPB = 1024;
 constexpr int NWAVE = TPB / WAVE;              // 16
-constexpr int RADIX_BITS = 11;
-constexpr int NBIN = 1 << RADIX_BITS;          // 2048 = 2 bins per thread
-constexpr int KEY_BITS = 63;
-constexpr uint64_t KEY_MASK = 0x7FFFFFFFFFFFFFFFull;
-constexpr int64_t CAP_DEFAULT = 4096;
 static_assert(NBIN == 2 * TPB, "pivot search owns two bins per thread");
-
-// Segment table: int64 [n_seg, SEG_COLS], one row per workgroup.
-enum { SEG_N, SEG_S, SEG_OUT, SEG_KEY, SEG_KIND, SEG_BASE, SEG_COLS };
-enum { KIND_PACK = 0, KIND_HALO = 1 };
-
-// ------------------------------------------------------------ key sources
-// key(word, i): the 63-bit key of position i of a segment whose SEG_KEY
-// column is `word`.
-struct PhiloxKeys {           // word = src_rank << 16 | dst_rank
-  uint32_t seed_lo, seed_hi, epoch;
-  DEV_INLINE uint64_t operator()(int64_t word, int i) const {
-    const P4 r = philox4x32((uint32_t)i, epoch, (uint32_t)word, 0x424E5347u,
-                            seed_lo, seed_hi);
-    return (((uint64_t)r.c0 << 32) | r.c1) & KEY_MASK;
-  }
-};
-
-struct RawKeys {              // word = offset of the segment in `keys`
-  const int64_t* __restrict__ keys;
-  DEV_INLINE uint64_t operator()(int64_t word, int i) const {
-    return (uint64_t)keys[word + i] & KEY_MASK;
-  }
-};
-
-struct SelectOut {
-  const int64_t* __restrict__ gather;     // boundary_cat, or null
-  const float* __restrict__ norm_full;    // per halo row, or null
-  const float* __restrict__ deg_full;
-  int64_t* __restrict__ pack;             // KIND_PACK values
-  int64_t* __restrict__ hsel;             // KIND_HALO values
-  float* __restrict__ norm;               // norm_full[hsel]
-  float* __restrict__ deg;                // deg_full[hsel]
-};
-
-// ------------------------------------------------------------ block steps
-// Exclusive prefix of v over the 1024 threads (wsum: NWAVE ints of LDS,
-// free again on return).
-DEV_INLINE int block_excl_scan(int v, int* wsum) {
-  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < WAVE; d <<= 1) {
-    const int u = __shfl_up(incl, d, WAVE);
-    if (lane >= d) incl += u;
-  }
-  if (lane == WAVE - 1) wsum[w] = incl;
-  __syncthreads();
-  int off = 0;
-#pragma unroll
-  for (int i = 0; i < NWAVE; ++i)
-    if (i < w) off += wsum[i];
-  __syncthreads();
-  return off + incl - v;
-}
-
-// Rank of the calling thread among the threads of the block with f set, in
-// thread order, and their number. wtot: NWAVE ints of LDS; consecutive
-// calls alternate between two such buffers, so that one barrier per call
-// is enough (a buffer is written again only two barriers later).
-DEV_INLINE int chunk_rank(bool f, int* wtot, int& total) {
-  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-  const uint64_t b = __ballot(f);
-  if (lane == 0) wtot[w] = __popcll(b);
-  __syncthreads();
-  int off = 0;
-  total = 0;
-#pragma unroll
-  for (int i = 0; i < NWAVE; ++i) {
-    const int t = wtot[i];
-    if (i < w) off += t;
-    total += t;
-  }
-  return off + __popcll(b & ((1ull << lane) - 1ull));
-}
 
 // ----------------------------------------------------------------- kernel
 template <class KeySrc, int CAP>
@@ -176,7 +104,7 @@ bns_select_kernel(const int64_t* __restrict__ segs, KeySrc ks, SelectOut o) {
       }
       __syncthreads();
       const int h0 = (int)hist[2 * tid], h1 = (int)hist[2 * tid + 1];
-      const int below = block_excl_scan(h0 + h1, wbuf[0]);
+      const int below = block_excl_scan<NWAVE>(h0 + h1, wbuf[0]);
       if (below < rank && rank <= below + h0) {
         piv[0] = 2 * tid; piv[1] = below; piv[2] = h0;
       } else if (below + h0 < rank && rank <= below + h0 + h1) {
@@ -220,7 +148,7 @@ bns_select_kernel(const int64_t* __restrict__ segs, KeySrc ks, SelectOut o) {
         const int i = i0 + tid;
         const bool eq = i < n && ks(word, i) == prefix;
         int tot;
-        const int k = seen + chunk_rank(eq, wbuf[par], tot);
+        const int k = seen + chunk_rank<NWAVE>(eq, wbuf[par], tot);
         par ^= 1;
         if (eq && k == rank - 1) { thr_key = prefix; thr_pos = i; }
         seen += tot;
@@ -242,20 +170,9 @@ bns_select_kernel(const int64_t* __restrict__ segs, KeySrc ks, SelectOut o) {
       sel = key < T || (key == T && i <= P);
     }
     int tot;
-    const int k = run + chunk_rank(sel, wbuf[par], tot);
+    const int k = run + chunk_rank<NWAVE>(sel, wbuf[par], tot);
     par ^= 1;
-    if (sel && k < cnt) {
-      const int64_t v = base + i;
-      if (kind == KIND_PACK) {
-        o.pack[out + k] = o.gather ? o.gather[v] : v;
-      } else {
-        o.hsel[out + k] = v;
-        if (o.norm_full) {
-          o.norm[out + k] = o.norm_full[v];
-          o.deg[out + k] = o.deg_full[v];
-        }
-      }
-    }
+    if (sel && k < cnt) o.emit(kind, out + k, base + i);
     run += tot;
   }
 }
@@ -279,11 +196,41 @@ void launch_select(int64_t cap, const at::Tensor& segs, const KeySrc& ks,
     TORCH_CHECK(false, "bns_select: cap must be ", CAP_DEFAULT, " or 64");
 }
 
-void check_segs(const at::Tensor& segs) {
-  TORCH_CHECK(segs.is_cuda() && segs.is_contiguous() && segs.dim() == 2 &&
-              segs.size(1) == SEG_COLS && segs.scalar_type() == at::kLong,
-              "segs: [n_seg, ", (int)SEG_COLS, "] int64 cuda tensor");
-}
+// The two tables of a call: `segs` for the one-workgroup kernel above,
+// `ssegs` with its (segment, slice) `items` for the sliced launches
+// (bns_select_sliced.hip). Either may be empty.
+struct Tables {
+  const at::Tensor& segs;
+  const at::Tensor& ssegs;
+  const at::Tensor& items;
+  int64_t slice_rows;
+
+  void check() const {
+    TORCH_CHECK(segs.is_cuda() && segs.is_contiguous() && segs.dim() == 2 &&
+                segs.size(1) == SEG_COLS && segs.scalar_type() == at::kLong,
+                "segs: [n_seg, ", (int)SEG_COLS, "] int64 cuda tensor");
+    TORCH_CHECK(ssegs.is_contiguous() && ssegs.dim() == 2 &&
+                ssegs.size(1) == SSEG_COLS &&
+                ssegs.scalar_type() == at::kLong &&
+                ssegs.device() == segs.device(),
+                "ssegs: [n_sseg, ", (int)SSEG_COLS, "] int64 tensor on the "
+                "device of segs");
+    TORCH_CHECK(items.is_contiguous() && items.dim() == 2 &&
+                items.size(1) == 2 && items.scalar_type() == at::kInt &&
+                items.device() == segs.device() &&
+                (items.size(0) > 0) == (ssegs.size(0) > 0),
+                "items: [n_item, 2] int32 tensor on the device of segs");
+    TORCH_CHECK(slice_rows > 0 && slice_rows % SLICE_TPB == 0 &&
+                slice_rows <= (1 << 30),
+                "slice_rows: a positive multiple of ", SLICE_TPB);
+  }
+
+  template <class KeySrc>
+  void launch(int64_t cap, const KeySrc& ks, const SelectOut& o) const {
+    launch_select(cap, segs, ks, o);
+    launch_select_sliced(cap, ssegs, items, slice_rows, ks, o);
+  }
+};
 
 const float* float_rows(const c10::optional<at::Tensor>& t, const char* name,
                         const at::Tensor& like) {
@@ -297,12 +244,14 @@ const float* float_rows(const c10::optional<at::Tensor>& t, const char* name,
 // The plan's entry: (pack_idx [n_pack], hsel [n_hsel], norm_full[hsel],
 // deg_full[hsel]); the two float outputs are empty without their sources.
 std::vector<at::Tensor> bns_select_philox(
-    const at::Tensor& segs, int64_t n_pack, int64_t n_hsel,
+    const at::Tensor& segs, const at::Tensor& ssegs, const at::Tensor& items,
+    int64_t slice_rows, int64_t n_pack, int64_t n_hsel,
     const c10::optional<at::Tensor>& boundary_cat,
     const c10::optional<at::Tensor>& norm_full,
     const c10::optional<at::Tensor>& deg_full, int64_t seed, int64_t epoch,
     int64_t cap) {
-  check_segs(segs);
+  const Tables tb{segs, ssegs, items, slice_rows};
+  tb.check();
   TORCH_CHECK(n_pack >= 0 && n_hsel >= 0, "bns_select: negative output size");
   TORCH_CHECK(norm_full.has_value() == deg_full.has_value(),
               "bns_select: norm_full and deg_full go together");
@@ -328,17 +277,18 @@ std::vector<at::Tensor> bns_select_philox(
   o.norm = norm.data_ptr<float>();
   o.deg = deg.data_ptr<float>();
   const uint64_t sd = (uint64_t)seed;
-  launch_select(cap, segs,
-                PhiloxKeys{(uint32_t)(sd & 0xFFFFFFFFull),
-                           (uint32_t)(sd >> 32), (uint32_t)epoch}, o);
+  tb.launch(cap, PhiloxKeys{(uint32_t)(sd & 0xFFFFFFFFull),
+                            (uint32_t)(sd >> 32), (uint32_t)epoch}, o);
   return {pack, hsel, norm, deg};
 }
 
 // The raw-key utility: positions (segment-local) of the s smallest keys of
 // every segment, ascending, concatenated ([n_out] int64).
 at::Tensor bns_select_raw(const at::Tensor& keys, const at::Tensor& segs,
-                          int64_t n_out, int64_t cap) {
-  check_segs(segs);
+                          const at::Tensor& ssegs, const at::Tensor& items,
+                          int64_t slice_rows, int64_t n_out, int64_t cap) {
+  const Tables tb{segs, ssegs, items, slice_rows};
+  tb.check();
   TORCH_CHECK(keys.is_cuda() && keys.is_contiguous() && keys.dim() == 1 &&
               keys.scalar_type() == at::kLong &&
               keys.device() == segs.device(),
@@ -348,7 +298,7 @@ at::Tensor bns_select_raw(const at::Tensor& keys, const at::Tensor& segs,
   at::Tensor out = at::empty({n_out}, segs.options());
   SelectOut o{};
   o.hsel = out.data_ptr<int64_t>();
-  launch_select(cap, segs, RawKeys{keys.data_ptr<int64_t>()}, o);
+  tb.launch(cap, RawKeys{keys.data_ptr<int64_t>()}, o);
   return out;
 }
 
@@ -359,15 +309,19 @@ namespace bns {
 void bind_bns_select(pybind11::module& m) {
   namespace py = pybind11;
   m.attr("BNS_SELECT_CAP") = CAP_DEFAULT;
+  m.attr("BNS_SELECT_SLICE_MIN") = (int64_t)SLICE_TPB;
   m.def("bns_select_philox", &bns_select_philox,
-        "per-epoch BNS selection of every plan segment in one launch "
+        "per-epoch BNS selection of every plan segment: `segs` in one "
+        "launch, `ssegs` sliced over `items` "
         "(pack_idx, hsel, norm_full[hsel], deg_full[hsel])",
-        py::arg("segs"), py::arg("n_pack"), py::arg("n_hsel"),
+        py::arg("segs"), py::arg("ssegs"), py::arg("items"),
+        py::arg("slice_rows"), py::arg("n_pack"), py::arg("n_hsel"),
         py::arg("boundary_cat"), py::arg("norm_full"), py::arg("deg_full"),
         py::arg("seed"), py::arg("epoch"), py::arg("cap") = CAP_DEFAULT);
   m.def("bns_select_raw", &bns_select_raw,
         "positions of the s smallest caller-supplied keys per segment",
-        py::arg("keys"), py::arg("segs"), py::arg("n_out"),
+        py::arg("keys"), py::arg("segs"), py::arg("ssegs"), py::arg("items"),
+        py::arg("slice_rows"), py::arg("n_out"),
         py::arg("cap") = CAP_DEFAULT);
 }
 

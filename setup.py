@@ -20,12 +20,14 @@ setup(
                      "bnsgcn_amd/ops/hip/gemm_tiled.hip",
                      "bnsgcn_amd/ops/hip/plan_build.hip",
                      "bnsgcn_amd/ops/hip/bn_fused.hip",
-                     "bnsgcn_amd/ops/hip/bns_select.hip"],
+                     "bnsgcn_amd/ops/hip/bns_select.hip",
+                     "bnsgcn_amd/ops/hip/bns_select_sliced.hip"],
             depends=["bnsgcn_amd/ops/hip/common.h",
                      "bnsgcn_amd/ops/hip/gemm_tiled.h",
                      "bnsgcn_amd/ops/hip/plan_build.h",
                      "bnsgcn_amd/ops/hip/bn_fused.h",
-                     "bnsgcn_amd/ops/hip/bns_select.h"],
+                     "bnsgcn_amd/ops/hip/bns_select.h",
+                     "bnsgcn_amd/ops/hip/bns_select_dev.h"],
             extra_compile_args={"nvcc": ["-O3"], "cxx": ["-O3"]},
         )
     ],
