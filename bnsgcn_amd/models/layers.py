@@ -270,3 +270,93 @@ class GATLayer(nn.Module):
         if self.bias is not None:
             out = out + self.bias.view(1, H, D)
         return out
+
+
+class GATv2Layer(nn.Module):
+    """GATv2 (--gat-attn v2): the non-linearity moves inside the dot
+    product, e = a · LeakyReLU(W_s h_src + W_d h_dst), so a destination's
+    ranking of its neighbours depends on the destination. The score is
+    F.gatv2_score (fused gather kernels, nothing of size [E, H, D] stored);
+    softmax, attention dropout and aggregation are GATLayer's, on the same
+    edge sets. Parameter names follow DGL GATv2Conv (fc_src, fc_dst, attn,
+    bias)."""
+
+    def __init__(self, in_feats, out_feats, heads, feat_drop=0.0, attn_drop=0.0,
+                 negative_slope=0.2, bias=True, use_pp=False):
+        super().__init__()
+        self.heads, self.out_feats = heads, out_feats
+        self.use_pp = use_pp
+        self.fc_src = nn.Linear(in_feats, heads * out_feats, bias=False)
+        self.fc_dst = nn.Linear(in_feats, heads * out_feats, bias=False)
+        self.attn = nn.Parameter(torch.empty(1, heads, out_feats))
+        self.bias = nn.Parameter(torch.zeros(heads * out_feats)) if bias else None
+        self.feat_drop = Dropout(feat_drop)
+        self.attn_drop = nn.Dropout(attn_drop)   # p only; fused in softmax2
+        self.negative_slope = negative_slope
+        gain = math.sqrt(2.0)
+        nn.init.xavier_normal_(self.fc_src.weight, gain=gain)
+        nn.init.xavier_normal_(self.fc_dst.weight, gain=gain)
+        nn.init.xavier_normal_(self.attn, gain=gain)
+
+    def _padded(self):
+        """(W_s, W_d, attn, Dp): the parameters with every head zero-padded
+        from D to Dp = pad4(D) outputs — the kernels read float4 slots of
+        one head. Zero pads add exact zeros to every score and every sum
+        (LeakyReLU(0 + 0) = 0), and autograd slices the gradients back."""
+        H, D = self.heads, self.out_feats
+        Dp = _pad4(D)
+        ws, wd, a = self.fc_src.weight, self.fc_dst.weight, self.attn
+        if Dp != D:
+            pad = torch.nn.functional.pad
+            ws = pad(ws.view(H, D, -1), (0, 0, 0, Dp - D)).reshape(H * Dp, -1)
+            wd = pad(wd.view(H, D, -1), (0, 0, 0, Dp - D)).reshape(H * Dp, -1)
+            a = pad(a, (0, Dp - D))
+        return ws, wd, a, Dp
+
+    def forward(self, ctx: GraphContext, x, halo_feat: torch.Tensor | None = None,
+                rows: torch.Tensor | None = None):
+        """Signature and the three paths (full-graph eval, split partition
+        block, loss-row restriction) of GATLayer.forward."""
+        from ..parallel.halo import halo_exchange
+
+        h = self.feat_drop(x)
+        H, D = self.heads, self.out_feats
+        ws, wd, attn, Dp = self._padded()
+        slope = self.negative_slope
+        if ctx.plan is None:                       # full-graph eval path
+            ip, ix, tip, tix, eperm, _ = ctx.gat_block()
+            zs = F.linear(h, ws).view(-1, H, Dp)
+            zd = F.linear(h, wd).view(-1, H, Dp)
+            logits = F.gatv2_score(zs, zd, attn, ip, ix, tip, tix, eperm, slope)
+            alpha = self.attn_drop(F.segment_softmax(logits, ip))
+            out = F.spmm_edge_sum(zs, alpha, ip, ix, tip, tix, eperm)
+        else:
+            if halo_feat is not None:              # layer 0 under use_pp
+                src_halo = self.feat_drop(halo_feat)
+                halo5 = ctx.gat_split_full()
+            else:
+                src_halo = halo_exchange(h, ctx.plan)
+                halo5 = ctx.gat_split_halo()
+            z_in = F.linear(h, ws).view(-1, H, Dp)
+            z_h = F.linear(src_halo, ws).view(-1, H, Dp)
+            if rows is not None:
+                # final-layer loss-row restriction: GATLayer's gathered
+                # edge sets; sources stay full, zd is computed for the
+                # labeled rows only
+                inner5 = ctx.gat_rows_inner()
+                halo5 = ctx.gat_rows_halo(ctx.plan.state)
+                zd = F.linear(h[rows], wd).view(-1, H, Dp)
+            else:
+                inner5 = (ctx.indptr, ctx.indices, ctx.t_indptr, ctx.t_indices,
+                          ctx.t_eperm)
+                zd = F.linear(h, wd).view(-1, H, Dp)
+            li = F.gatv2_score(z_in, zd, attn, *inner5, slope)
+            lh = F.gatv2_score(z_h, zd, attn, *halo5, slope)
+            p_attn = self.attn_drop.p if self.training else 0.0
+            ai, ah = F.segment_softmax2(li, lh, inner5[0], halo5[0],
+                                        p_drop=p_attn)
+            out = F.spmm_edge_sum2(z_in, ai, z_h, ah, inner5, halo5)
+        out = out[..., :D]
+        if self.bias is not None:
+            out = out + self.bias.view(1, H, D)
+        return out

@@ -16,7 +16,8 @@ import torch.nn.functional as TF
 
 from ..ops import functional as F
 from .context import GraphContext
-from .layers import GCNLayer, SAGELayer, GATLayer, LayerNorm, Dropout
+from .layers import (GCNLayer, SAGELayer, GATLayer, GATv2Layer, LayerNorm,
+                     Dropout)
 from .sync_bn import SyncBatchNorm
 
 
@@ -132,15 +133,18 @@ class GraphSAGE(GCN):
 
 class GAT(GNNBase):
     def __init__(self, layer_size, activation, use_pp=False, heads=1,
-                 dropout=0.5, norm="layer", n_linear=0, train_size=None):
+                 dropout=0.5, norm="layer", n_linear=0, train_size=None,
+                 attn="v1"):
         super().__init__(layer_size, activation, use_pp, dropout, norm,
                          n_linear, train_size)
+        # attn: "v1" = GATLayer (static attention), "v2" = GATv2Layer
+        conv = {"v1": GATLayer, "v2": GATv2Layer}[attn]
         for i in range(self.n_layers):
             if i < self.n_layers - self.n_linear:
-                self.layers.append(GATLayer(layer_size[i], layer_size[i + 1],
-                                            heads, feat_drop=dropout,
-                                            attn_drop=dropout,
-                                            use_pp=(use_pp and i == 0)))
+                self.layers.append(conv(layer_size[i], layer_size[i + 1],
+                                        heads, feat_drop=dropout,
+                                        attn_drop=dropout,
+                                        use_pp=(use_pp and i == 0)))
             else:
                 self.layers.append(nn.Linear(layer_size[i], layer_size[i + 1]))
 
@@ -181,6 +185,7 @@ def create_model(args, n_feat, n_class, train_size) -> nn.Module:
     SAGELayer); GAT forces use_pp semantics the reference way
     (train.py:222: GAT always use_pp=True)."""
     import torch.nn.functional as TF
+    from ..runtime.config import gat_attn_of
     hidden = [args.n_hidden] * (args.n_layers - 1)
     layer_size = [n_feat] + hidden + [n_class]
     act = TF.relu
@@ -194,5 +199,6 @@ def create_model(args, n_feat, n_class, train_size) -> nn.Module:
     if args.model == "gat":
         return GAT(layer_size, act, use_pp=True, heads=args.heads,
                    dropout=args.dropout, norm=args.norm,
-                   n_linear=args.n_linear, train_size=train_size)
+                   n_linear=args.n_linear, train_size=train_size,
+                   attn=gat_attn_of(args))
     raise ValueError(f"unknown model {args.model}")

@@ -240,6 +240,41 @@ def sddmm_add_raw(indptr, indices, el_src, er_dst, slope=-1.0):
     return out
 
 
+def gatv2_score_raw(indptr, indices, zs, zd, attn, slope):
+    """e[k,h] = Σ_d attn[h,d]·LeakyReLU(zs[col_k,h,d] + zd[row_k,h,d]) on
+    the fused HIP gather kernel (fp32, D % 4 == 0, H·D <= 1024 — anything
+    else raises there: no eager fallback on the GPU)."""
+    if zd.shape[0] != indptr.numel() - 1:
+        raise ValueError(f"gatv2_score: zd has {zd.shape[0]} rows, the CSR "
+                         f"{indptr.numel() - 1}")
+    if use_hip(zs):
+        wl = _worklist_of(indptr)[:4]
+        return get_ext().gatv2_score(*wl, indices, zs.contiguous(),
+                                     zd.contiguous(), attn.contiguous(),
+                                     float(slope))
+    return ref.gatv2_score(indptr, indices, zs, zd, attn, slope)
+
+
+def gatv2_score_bwd_raw(indptr, indices, eperm, g, z_res, z_str, attn, slope,
+                        want_dattn=False):
+    """Backward of gatv2_score for the operand indexed by the ROWS of the
+    CSR given (ref.gatv2_score_backward): forward CSR with (z_res, z_str) =
+    (zd, zs) for d zd, transposed CSR + its eperm with (zs, zd) for d zs.
+    Returns (dz_res, dattn [H, D] or None)."""
+    if z_res.shape[0] != indptr.numel() - 1:
+        raise ValueError(f"gatv2_score_bwd: z_res has {z_res.shape[0]} rows, "
+                         f"the CSR {indptr.numel() - 1}")
+    if use_hip(g):
+        ret = get_ext().gatv2_score_bwd(
+            *_worklist_of(indptr), indices, eperm, g.contiguous(),
+            z_res.contiguous(), z_str.contiguous(), attn.contiguous(),
+            float(slope), want_dattn)
+        return ret[0], (ret[1] if want_dattn else None)
+    dz, dattn = ref.gatv2_score_backward(indptr, indices, g, z_res, z_str,
+                                         attn, slope, eperm)
+    return dz, (dattn if want_dattn else None)
+
+
 def segment_softmax_raw(indptr, logits):
     if use_hip(logits):
         return get_ext().segment_softmax(indptr, logits)
@@ -461,6 +496,47 @@ def sddmm_add(el, er, indptr, indices, indptr_t, indices_t, eperm_t,
               slope=None):
     return _SDDMMAdd.apply(el, er, indptr, indices, indptr_t, indices_t,
                            eperm_t, slope)
+
+
+class _GATv2Score(Function):
+    """GATv2 logits (gatv2_score_raw). Saves zs, zd, attn and the CSRs —
+    nothing per (edge, feature): the backward kernels recompute
+    s = zs[col] + zd[row] from the rows they gather. d zd and d attn come
+    from one pass over the forward CSR, d zs from one over the transposed
+    CSR with eperm fused into the load of the gradient."""
+
+    @staticmethod
+    def forward(ctx, zs, zd, attn, indptr, indices, indptr_t, indices_t,
+                eperm_t, slope):
+        ctx.save_for_backward(zs, zd, attn, indptr, indices, indptr_t,
+                              indices_t, eperm_t)
+        ctx.slope = float(slope)
+        return gatv2_score_raw(indptr, indices, zs, zd, attn, ctx.slope)
+
+    @staticmethod
+    def backward(ctx, grad):
+        (zs, zd, attn, indptr, indices, indptr_t, indices_t,
+         eperm_t) = ctx.saved_tensors
+        grad = grad.contiguous()
+        g_zs = g_zd = g_attn = None
+        need_zs, need_zd, need_attn = ctx.needs_input_grad[:3]
+        if need_zd or need_attn:
+            g_zd, g_attn = gatv2_score_bwd_raw(
+                indptr, indices, None, grad, zd, zs, attn, ctx.slope,
+                want_dattn=need_attn)
+            if need_attn:
+                g_attn = g_attn.reshape(attn.shape)
+        if need_zs:
+            g_zs = gatv2_score_bwd_raw(indptr_t, indices_t, eperm_t, grad,
+                                       zs, zd, attn, ctx.slope)[0]
+        return (g_zs, g_zd if need_zd else None, g_attn) + (None,) * 6
+
+
+def gatv2_score(zs, zd, attn, indptr, indices, indptr_t, indices_t, eperm_t,
+                slope):
+    """zs [n_src, H, D], zd [n_dst, H, D], attn H·D values -> e [E, H]."""
+    return _GATv2Score.apply(zs, zd, attn, indptr, indices, indptr_t,
+                             indices_t, eperm_t, slope)
 
 
 class _SegmentSoftmax(Function):

@@ -82,6 +82,43 @@ def sddmm_add(indptr: torch.Tensor, indices: torch.Tensor,
     return el_src[indices.long()] + er_dst[row]
 
 
+def gatv2_score(indptr: torch.Tensor, indices: torch.Tensor,
+                zs: torch.Tensor, zd: torch.Tensor, attn: torch.Tensor,
+                slope: float) -> torch.Tensor:
+    """GATv2 attention logits: out[e, h] = sum_d attn[h, d] *
+    LeakyReLU(zs[col_e, h, d] + zd[row_e, h, d]).
+
+    zs: [n_src, H, D]; zd: [n_rows, H, D]; attn: H * D values; returns
+    [E, H]."""
+    s = zs[indices.long()] + zd[_row_of_edge(indptr)]
+    act = torch.where(s > 0, s, s * slope)
+    return (act * attn.reshape(1, *zs.shape[1:])).sum(-1)
+
+
+def gatv2_score_backward(indptr: torch.Tensor, indices: torch.Tensor,
+                         g: torch.Tensor, z_res: torch.Tensor,
+                         z_str: torch.Tensor, attn: torch.Tensor,
+                         slope: float, eperm: torch.Tensor | None = None):
+    """Backward of gatv2_score for the operand indexed by the rows of the
+    CSR it is given (z_res; z_str is the one indexed by the columns), with
+    m = s > 0 ? 1 : slope and g' = g[eperm] if eperm is given:
+
+        dz_res[r, h, d] = attn[h, d] * sum_{e in row r} g'[e, h] * m[e, h, d]
+        dattn[h, d]     = sum_e g'[e, h] * LeakyReLU(s[e, h, d])
+
+    Forward CSR, (z_res, z_str) = (zd, zs): d zd. Transposed CSR with its
+    edge permutation, (zs, zd): d zs. Returns (dz_res, dattn [H, D])."""
+    H, D = z_res.shape[1], z_res.shape[2]
+    row = _row_of_edge(indptr)
+    s = z_str[indices.long()] + z_res[row]
+    gp = (g if eperm is None else g[eperm]).unsqueeze(-1)
+    pos = s > 0
+    dz = torch.zeros_like(z_res)
+    dz.index_add_(0, row, torch.where(pos, gp, gp * slope))
+    dattn = (gp * torch.where(pos, s, s * slope)).sum(0)
+    return dz * attn.reshape(1, H, D), dattn
+
+
 def segment_softmax(indptr: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
     """Numerically stable softmax over each CSR row's edges.
     logits: [E, H] grouped by row in CSR order. Returns [E, H]."""

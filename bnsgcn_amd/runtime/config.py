@@ -95,7 +95,32 @@ def create_parser() -> argparse.ArgumentParser:
                         "gradient (backward) once and reads 16-byte bf16 "
                         "rows; attention, sums and outputs stay fp32. "
                         "Default: $BNSGCN_GAT_DTYPE, else fp32")
+    p.add_argument("--gat-attn", "--gat_attn", choices=["v1", "v2"],
+                   default=os.environ.get("BNSGCN_GAT_ATTN", "v1"),
+                   help="GAT attention: v1 = a_l.z_src + a_r.z_dst under "
+                        "the LeakyReLU (static ranking); v2 = GATv2, "
+                        "a . LeakyReLU(W_s h_src + W_d h_dst), on fused fp32 "
+                        "HIP score kernels. Default: $BNSGCN_GAT_ATTN, "
+                        "else v1")
     return p
+
+
+def gat_attn_of(args):
+    """"v1" or "v2" of --gat-attn, validated like gat_dtype_of: v2 is a
+    variant of the GAT model only, and its score kernels are fp32."""
+    name = getattr(args, "gat_attn", "v1")
+    if name not in ("v1", "v2"):
+        raise ValueError(f"--gat-attn must be v1 or v2, got {name!r}")
+    if name == "v2" and getattr(args, "model", None) != "gat":
+        raise ValueError(
+            "--gat-attn v2 is a variant of --model gat; use --gat-attn v1 "
+            "(and unset BNSGCN_GAT_ATTN) with --model gcn/graphsage.")
+    if name == "v2" and getattr(args, "gat_dtype", "fp32") == "bf16":
+        raise ValueError(
+            "--gat-attn v2 with --gat-dtype bf16: the v2 score kernels are "
+            "fp32 and have no bf16-source form; use --gat-dtype fp32 (and "
+            "unset BNSGCN_GAT_DTYPE) with --gat-attn v2.")
+    return name
 
 
 def gat_dtype_of(args):

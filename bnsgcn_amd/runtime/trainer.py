@@ -31,7 +31,7 @@ from ..models.models import create_model
 from ..ops.functional import pack_rows_raw, spmm_sum_raw
 from ..parallel import GradReducer, HaloPlan, all_to_all_rows, init_distributed
 from ..utils.timer import comm_timer
-from .config import agg_dtype_of, gat_dtype_of, graph_name_of
+from .config import agg_dtype_of, gat_attn_of, gat_dtype_of, graph_name_of
 
 
 # --------------------------------------------------------------- offline
@@ -134,6 +134,7 @@ class RankState:
     def __init__(self, part: Partition, args, device):
         agg_dtype = agg_dtype_of(args)      # raises on gat + bf16
         gat_dtype = gat_dtype_of(args)      # raises on gcn/graphsage + bf16
+        gat_attn_of(args)                   # raises on v2 without gat / + bf16
         self.device = torch.device(device)
         self.part = part
         self.args = args
@@ -385,6 +386,7 @@ def run(args, rank: int | None = None, world_size: int | None = None) -> dict:
     # aborts the whole job (same guard as bench.py:88-96)
     agg_dtype_of(args)      # --agg-dtype bf16 with GAT: fail at start-up
     gat_dtype_of(args)      # --gat-dtype bf16 without GAT: likewise
+    gat_attn_of(args)       # --gat-attn v2 without GAT or with bf16: likewise
     pre_rank = int(os.environ.get("RANK", rank if rank is not None else 0))
     pre_world = int(os.environ.get("WORLD_SIZE",
                                    world_size if world_size is not None else 1))

@@ -12,7 +12,8 @@ import os
 import torch.multiprocessing as mp
 
 from bnsgcn_amd.runtime.config import (agg_dtype_of, create_parser,
-                                       gat_dtype_of, graph_name_of)
+                                       gat_attn_of, gat_dtype_of,
+                                       graph_name_of)
 from bnsgcn_amd.runtime.trainer import prepare_partitions, run
 
 
@@ -29,6 +30,7 @@ def main():
     args = create_parser().parse_args()
     agg_dtype_of(args)      # --agg-dtype bf16 + --model gat: fail before work
     gat_dtype_of(args)      # --gat-dtype bf16 without --model gat: likewise
+    gat_attn_of(args)       # --gat-attn v2 without --model gat: likewise
     args.graph_name = graph_name_of(args)
     if args.node_rank == 0 and not args.skip_partition:
         prepare_partitions(args)

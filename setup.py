@@ -21,8 +21,12 @@ setup(
                      "bnsgcn_amd/ops/hip/plan_build.hip",
                      "bnsgcn_amd/ops/hip/bn_fused.hip",
                      "bnsgcn_amd/ops/hip/bns_select.hip",
-                     "bnsgcn_amd/ops/hip/bns_select_sliced.hip"],
+                     "bnsgcn_amd/ops/hip/bns_select_sliced.hip",
+                     "bnsgcn_amd/ops/hip/gatv2.hip"],
             depends=["bnsgcn_amd/ops/hip/common.h",
+                     "bnsgcn_amd/ops/hip/gather_stream.h",
+                     "bnsgcn_amd/ops/hip/worklist_launch.h",
+                     "bnsgcn_amd/ops/hip/gatv2.h",
                      "bnsgcn_amd/ops/hip/gemm_tiled.h",
                      "bnsgcn_amd/ops/hip/plan_build.h",
                      "bnsgcn_amd/ops/hip/bn_fused.h",
